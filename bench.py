@@ -8,7 +8,9 @@ faces (BASELINE.json metric), one process per GPU.
   python bench.py --gpus N ...            (no launcher: starts the N ranks itself, as a child torch.distributed.run)
 
 A step = Model.training_step (zero_grad, backbone fwd, normalise, margin-softmax head, backward, clip, SGD step)
-on a pre-staged synthetic batch.  Rank 0 prints ONE JSON line.  `roofline` is measured live: every launch of the
+on a pre-staged synthetic batch.  Rank 0 prints ONE JSON line.  `--dump-outputs DIR` also writes what the last timed step
+produced (its loss and the model state it left, larger tensors as a fixed seeded sample) to DIR/<name>.npy, so that two builds
+can be compared output for output on identical seeded inputs.  `roofline` is measured live: every launch of the
 dominant kernel (the bf16 MFMA implicit-GEMM conv, forward + data-gradient) inside the timed region is bracketed
 by HIP events on the stream it runs on; achieved = algorithmic FLOPs of those launches / their summed duration.
 `cpu_baseline` times the CPU restatement (oracle/) of the same step on the host cores (rank 0, N=1 only).
@@ -26,11 +28,6 @@ PKG = os.path.join(ROOT, "face-recognition-pytorch_amd")
 for p in (ROOT, PKG):
     if p not in sys.path:
         sys.path.insert(0, p)
-
-# More hardware queues than HIP's default of 4: with RCCL's and the process group's streams alive, the weight-gradient side
-# stream must not be multiplexed onto the main stream's queue (nets/_backbone.side_stream also probes for that at run time).
-# Read by the HIP runtime when it initialises, i.e. at the first device call, not at import.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
@@ -304,6 +301,38 @@ def extra_config(network, batch, fp8, classes, steps=10, warmup=3):
     return rec
 
 
+DUMP_BYTES = 60 << 20          # --dump-outputs stays under 64 MB in all: the array data, with room for the .npy headers
+
+
+def dump_outputs(path, model, loss):
+    """Write what one training step hands its caller -- the loss, and the model state it leaves behind (encoder.<key>: parameters
+    and BatchNorm statistics; head.<key>: class centres) -- to path/<name>.npy, floating tensors as float32, integer ones as float64.
+    With PartialFC sampling (rate < 1) head.weight is the full class-centre buffer, into which the sampled rows are written back only
+    when the next step samples (PartialFC.update), so the rows the step itself updated are dumped as head.weight_activated.  Every
+    array gets an equal share of DUMP_BYTES; a larger tensor is reduced to a fixed sample of distinct positions drawn from a generator
+    seeded by the tensor's name, so that another build of the project samples the same positions."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    state = [(part + "." + k, v.detach()) for part, mod in (("encoder", model.encoder), ("head", model.loss))
+             for k, v in mod.state_dict().items() if v.numel()]
+    if getattr(model.loss, "sample_rate", 1.0) < 1:
+        state.append(("head.weight_activated", model.loss.weight_activated.detach()))
+    share = DUMP_BYTES // (len(state) + 1)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy())
+    total = 0
+    for k, v in state:
+        fp = v.is_floating_point()
+        flat, cap = v.reshape(-1), share // (4 if fp else 8)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(flat.numel(), cap, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float32 if fp else torch.float64).cpu().numpy()
+        np.save(os.path.join(path, k + ".npy"), a)
+        total += a.nbytes
+    log("outputs of the last timed step: %d arrays, %.1f MB in %s" % (len(state) + 1, total / 2**20, path))
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
@@ -353,7 +382,11 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the cfg 4 / cfg 5 runs that follow the headline measurement")
     ap.add_argument("--dist-path", action="store_true",
                     help="rehearse the N>1 code path (RCCL group, DDP wrap, PartialFC rate 0.1) in a 1-rank group")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last one's loss and the model state it left to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     args.img_size = 192 if args.network.startswith("AlterNet") else 112
     if args.batch is None:
         args.batch = 256 if args.network.startswith("AlterNet") else BATCH
@@ -436,6 +469,8 @@ def main():
         out = model.training_step((img, ids.clone()))
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:              # before the instrumented steps below move the model on
+        dump_outputs(args.dump_outputs, model, out["loss"])
     # Dominant-kernel durations INSIDE running steps: the same loop again, now with two HIP events around every conv launch.
     # Kept out of the timed region above: the ~230 event records per step cost 0.6-0.7 ms of a 27-ms step (measured), which
     # would be charged to `value`; the instrumented steps run right behind the timed ones in the same process and state.

@@ -5,8 +5,9 @@
 // read with the gfx950 transposing LDS read ds_read_b64_tr_b16 (bf16) / strided ds_read_b32 (f32 validation mode).
 // Tile: 4 waves (2x2); LDS rows are RB = 256 or 128 bytes of channels; 64 pixels per K step; two stages filled
 // by LDS-DMA with the 16-byte chunks XOR-swizzled on the source side so both the DMA image and the transposed
-// reads are bank-conflict free.  Split-K over pixel ranges; results are added with fp32 atomics in whole
-// 256-byte rows staged through LDS.
+// reads are bank-conflict free.  Split-K over pixel ranges; each K split stores its partial tiles to a private slab
+// of the caller's workspace and one reduce pass adds the slabs in split order (run-to-run identical); a single split
+// adds its tiles into the output directly, in whole 256-byte rows staged through LDS.
 // Reference counterpart: autograd of nn.Conv2d / F.linear (cuDNN wgrad), nets/resnet.py:23-46, nets/PartialFC.py:201.
 #include <cstdlib>
 #include "common.h"
@@ -40,7 +41,7 @@ struct TnGeom {
     int M, Kc, ldp;          // GEMM-K rows, valid P columns (= output rows), P row pitch (elements)
     int ksteps, ksteps_per_split;
     FastDiv d_howo, d_wo;
-    int slab_stride;             // 0: add into `out` with fp32 atomics; > 0: each K split stores its tiles into out + split*slab_stride
+    int slab_stride;             // 0: one K split, added into `out` (each element once); > 0: each K split stores its tiles into out + split*slab_stride
     int adv_wo, adv_ho, adv_n;   // 64 pixels = adv_n images + adv_ho rows + adv_wo columns (mixed-radix step per K step)
     uint32_t p_bytes, q_bytes;
     // operand transform of the nine-tap kernel (XF instantiations): Q is the INPUT of a BatchNorm + ReLU and the weight
@@ -115,7 +116,7 @@ __device__ __forceinline__ void tn_epilogue(f32x4_t (&acc)[NT][NT], char* smem, 
     static_assert(NT == Tile::NT, "accumulator shape");
     const int lane = lane_id(), wave = wave_id();
     const int wco = wave >> 1, wci = wave & 1;
-    // ---- epilogue: D[row = co (4g+reg)][col = ci (lane&15)] -> LDS [co][ci] fp32 -> row-wise atomic adds
+    // ---- epilogue: D[row = co (4g+reg)][col = ci (lane&15)] -> LDS [co][ci] fp32 -> row-wise slab stores (one split: adds into out)
     __syncthreads();
     constexpr int P = Tile::OUT_PITCH;
     char* mine = smem + wave * Tile::WC * P;
@@ -1090,13 +1091,23 @@ static int tn_launch(const TnGeom& g, const void* p, const void* q, float* out, 
     return check_launch("igemm_tn");
 }
 
+// K splits that added their partial tiles into `out` with fp32 atomics would sum them in whatever order they land, and the
+// weight gradient would change from run to run.  So a launch uses no more K splits than the workspace has slabs for (one split
+// -- each element added once -- where the slab path is closed).
+static int tn_slab_splits(int splits, size_t out_elems, const float* ws, size_t ws_bytes) {
+    if (splits <= 1) return splits;
+    if (!ws || (out_elems % 4)) return 1;
+    const size_t fit = ws_bytes / (out_elems * sizeof(float));
+    return fit < 1 ? 1 : ((size_t)splits > fit ? (int)fit : splits);
+}
+
 // Decide where the K splits put their results: private slabs in the caller's workspace (plain stores + one
-// deterministic reduce pass) when it is large enough, else fp32 atomics straight into `out`.
+// deterministic reduce pass) when there is more than one split, else (one split) straight into `out`.
 static float* tn_pick_dst(TnGeom& g, float* out, int splits, size_t out_elems, float* ws, size_t ws_bytes) {
     g.slab_stride = 0;
     // same-address fp32 atomics from hundreds of K splits serialise in L2 (75 us for 500 splits of a 147 KB tile);
     // slabs + a grouped reduce pass cost two streaming passes over splits * out bytes instead
-    if (splits > 1 && ws && (out_elems % 4) == 0 && out_elems >= 16384 &&
+    if (splits > 1 && ws && (out_elems % 4) == 0 &&
         (size_t)splits * out_elems * sizeof(float) <= ws_bytes) {
         g.slab_stride = (int)out_elems;
         return ws;
@@ -1228,9 +1239,10 @@ static int tn_run(int dtype, const void* p, const void* q, float* out, int n, in
         }
         if (splits <= 0) splits = best;
         if (splits > g.ksteps) splits = g.ksteps;
+        splits = (kc % 4 == 0) ? tn_slab_splits(splits, out_elems, ws, ws_bytes) : 1;                 // slab layout packs co in fours
         g.ksteps_per_split = (g.ksteps + splits - 1) / splits;
         splits = (g.ksteps + g.ksteps_per_split - 1) / g.ksteps_per_split;
-        float* dst = (kc % 4 == 0) ? tn_pick_dst(g, out, splits, out_elems, ws, ws_bytes) : out;      // slab layout packs co in fours
+        float* dst = tn_pick_dst(g, out, splits, out_elems, ws, ws_bytes);
         const bool deep = !wide && 64 + 2 * w + 2 <= 128;      // three stages of a 128-row window
         // W <= 14: a 96-row window, 20-KB stages -- FOUR fit the co-resident tile's 82-KB request, so an operand load has three K steps to land
         const bool deep4 = deep && g_t9_stages4 && 64 + 2 * w + 2 <= 96 && !xf_scale;
@@ -1250,7 +1262,7 @@ static int tn_run(int dtype, const void* p, const void* q, float* out, int n, in
     const bool big = (c * es >= 256) && (kc * es >= 256);
     if (splits <= 0) {
         // Split-K heuristic: the grid should fill whole "rounds" of the chip (256 CUs x resident workgroups) with as
-        // few splits as possible -- every extra split adds a full fp32 atomic pass over the output tile and a
+        // few splits as possible -- every extra split adds a full slab of the output tile to store and to reduce, and a
         // partially filled last round wastes up to a third of the launch.
         const int bc = (big ? 256 : 128) / es;
         const long long tiles = 1LL * ((kc + bc - 1) / bc) * ((c + bc - 1) / bc) * taps;
@@ -1270,6 +1282,7 @@ static int tn_run(int dtype, const void* p, const void* q, float* out, int n, in
         splits = best;
     }
     if (splits > g.ksteps) splits = g.ksteps;
+    splits = tn_slab_splits(splits, out_elems, ws, ws_bytes);
     g.ksteps_per_split = (g.ksteps + splits - 1) / splits;
     splits = (g.ksteps + g.ksteps_per_split - 1) / g.ksteps_per_split;
     if (overwrite && splits == 1) {

@@ -38,3 +38,30 @@ def test_bench_cli_defaults_match_the_contract():
     for flag in ("--gpus", "--steps", "--warmup"):
         assert flag in src
     assert 'default=1)' in src                               # --gpus defaults to one GPU
+
+
+def test_dump_outputs_is_seeded_and_bounded(tmp_path):
+    """--dump-outputs: one .npy per state entry plus the loss, float32 / float64 only, under 64 MB however large the model, and the
+    same sampled positions from run to run"""
+    import sys
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    m = torch.nn.Module()
+    m.encoder = torch.nn.Sequential(torch.nn.Conv2d(512, 512, 3), torch.nn.BatchNorm2d(512)).bfloat16()
+    m.loss = torch.nn.Module()
+    m.loss.register_buffer("weight", torch.randn(40000, 512))       # 80 MB in fp32: must be sampled
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), m, torch.tensor(1.5))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(["loss.npy", "head.weight.npy"] + ["encoder.%s.npy" % k for k, v in m.encoder.state_dict().items() if v.numel()])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 << 20
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == 1.5
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "encoder.1.running_var.npy"), np.ones(512, np.float32))
+    w = np.load(tmp_path / "a" / "head.weight.npy")
+    assert 0 < w.size < 40000 * 512 and np.isin(w, m.loss.weight.numpy()).all()

@@ -369,5 +369,5 @@ def test_head_update_during_backward_is_one_shot_and_bit_identical(pg):
                      next(m.encoder.parameters()).data.clone()))
     assert not torch.equal(outs[0][0], w0)
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])      # class centres + momentum: bit-identical
-    # (the encoder's small 1x1 weight gradients are summed with fp32 atomics: equal to rounding, not to the bit, run to run)
+    # (the encoder is held to rounding here; run-to-run identity of its gradients is tests/test_run_to_run_gpu.py's subject)
     torch.testing.assert_close(outs[0][2], outs[1][2], rtol=1e-5, atol=1e-6)

@@ -9,7 +9,6 @@ import types
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "face-recognition-pytorch_amd")]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import torch.distributed as dist
 
