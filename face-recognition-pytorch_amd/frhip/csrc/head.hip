@@ -7,12 +7,25 @@
 //   nets/PartialFC.py:198-204 normalize + linear + clamp, nets/ArcFace.py:76-91 margin,
 //   nets/PartialFC.py:441-484 DistCrossEntropyFunc forward/backward.
 // Cross-rank steps (all-reduce MAX / SUM of the per-row scalars) are done by the host between these kernels.
+// The other margin modules of the reference (nets/ArcFace.py:5-61 CombinedMarginLoss with interclass filtering and easy_margin,
+// :94-106 CosFace) are compile-time variants of the same epilogue (template arguments MK, FILT of head_kernel).
 #include "igemm_nt.h"
 #include "frhip.h"
 
 namespace frhip {
 
 struct MarginConst { float s, cos_m, sin_m, theta, sinmm; };
+struct MarginConstEx : MarginConst { float m3, thr; };       // CosFace margin, interclass-filtering threshold
+
+// margin variants of the head epilogue.  The ArcFace kernel (the reference default, bench.py) keeps the plain MarginConst
+// argument, so its kernel-argument layout and code are exactly those it had before the variants existed.
+// (named constants and a traits struct, not an unnamed enum in std::conditional: the kernels' mangled names must come out the same in the
+// host and the device compilation, and an unnamed type is numbered differently in the two)
+constexpr int MG_ARC = 0, MG_ARC_EASY = 1, MG_COS = 2;
+template <int MK, bool FILT> struct MarginArgOf { typedef MarginConstEx type; };
+template <> struct MarginArgOf<MG_ARC, false> { typedef MarginConst type; };
+template <int MK, bool FILT>
+using MarginArg = typename MarginArgOf<MK, FILT>::type;
 
 // one wave per row: xhat = x / max(|x|, eps) (T), norm (fp32)
 template <typename T>
@@ -101,10 +114,14 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
 // ---------------------------------------------------------------------------------------------------------
 // FWD = true : partial row max / sum-exp per 64-class column group, target logit.
 // FWD = false: dT tile (compute dtype) from the recomputed cosines and the global row max / sum.
-template <typename T, bool FWD>
+// MK: MG_ARC (cos(theta + m), below cos(pi - m) t - m sin(pi - m)), MG_ARC_EASY (cos(theta + m) for t > 0, else t), MG_COS (t - m3).
+// FILT: interclass filtering (reference nets/ArcFace.py:28-39): an element that is not its row's target and whose clamped cosine is
+// > thr is multiplied by 0 -- logit 0, which still counts in the softmax sum, and d/dcos 0 (the reference builds the mask under
+// no_grad); a row without a target on this shard (label -1) is filtered in every column.
+template <typename T, bool FWD, int MK, bool FILT>
 __global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __restrict__ ehat,
                                                              const void* __restrict__ what, const int* __restrict__ labels,
-                                                             MarginConst mc, float* __restrict__ part_max,
+                                                             MarginArg<MK, FILT> mc, float* __restrict__ part_max,
                                                              float* __restrict__ part_sum, float* __restrict__ ztarget,
                                                              const float* __restrict__ rowmax, const float* __restrict__ rowsum,
                                                              float gscale, const float* __restrict__ upstream,
@@ -142,10 +159,20 @@ __global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __re
                 const float raw = ml.acc[nt][mt][e];
                 float t = fminf(fmaxf(raw, -1.f), 1.f);
                 float slope = 1.f;
+                bool filtered = false;
                 if (cls == lab) {
-                    const float sin_t = sqrtf(1.f - t * t);
-                    if (t > mc.theta) { slope = mc.cos_m + t * mc.sin_m / sin_t; t = t * mc.cos_m - sin_t * mc.sin_m; }
-                    else t = t - mc.sinmm;
+                    if constexpr (MK == MG_ARC) {
+                        const float sin_t = sqrtf(1.f - t * t);
+                        if (t > mc.theta) { slope = mc.cos_m + t * mc.sin_m / sin_t; t = t * mc.cos_m - sin_t * mc.sin_m; }
+                        else t = t - mc.sinmm;
+                    } else if constexpr (MK == MG_ARC_EASY) {
+                        const float sin_t = sqrtf(1.f - t * t);
+                        if (t > 0.f) { slope = mc.cos_m + t * mc.sin_m / sin_t; t = t * mc.cos_m - sin_t * mc.sin_m; }
+                    } else {
+                        t = t - mc.m3;
+                    }
+                } else if constexpr (FILT) {
+                    if (t > mc.thr) { t = 0.f; filtered = true; }
                 }
                 const float zz = t * mc.s;
                 if (FWD) {
@@ -156,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __re
                     float d = 0.f;
                     if (cls < g.Nout && mrow) {
                         const float p = __expf(zz - gm) * gs;
-                        const bool inside = raw >= -1.f && raw <= 1.f;
+                        const bool inside = raw >= -1.f && raw <= 1.f && !filtered;
                         d = inside ? (p - (cls == lab ? 1.f : 0.f)) * gscale * mc.s * slope : 0.f;
                     }
                     ml.acc[nt][mt][e] = d;
@@ -294,14 +321,15 @@ __global__ void head_loss_kernel(const float* __restrict__ q, int N, float* __re
     if (threadIdx.x == 0) loss[0] = -red[0] / (float)N;
 }
 
-template <typename T, bool FWD>
-static int head_launch(const NtGeom& g, const void* ehat, const void* what, const int* labels, const MarginConst& mc,
-                       float* pmax, float* psum, float* zt, const float* rmax, const float* rsum, float gscale,
-                       const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
+template <typename T, bool FWD, int MK, bool FILT>
+static int head_launch_mk(const NtGeom& g, const void* ehat, const void* what, const int* labels, const MarginConstEx& mcx,
+                          float* pmax, float* psum, float* zt, const float* rmax, const float* rsum, float gscale,
+                          const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
     typedef NtTile<T, 2, 2> Tile;
     const int mtiles = (g.M + Tile::BM - 1) / Tile::BM, ntiles = (g.Nout + Tile::BN - 1) / Tile::BN;
     const int lds = Tile::template lds_bytes<T>();
-    auto kern = head_kernel<T, FWD>;
+    const MarginArg<MK, FILT> mc = mcx;           // plain ArcFace: the MarginConst part only
+    auto kern = head_kernel<T, FWD, MK, FILT>;
     static bool attr_done = false;
     if (!attr_done) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
@@ -313,6 +341,24 @@ static int head_launch(const NtGeom& g, const void* ehat, const void* what, cons
     hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(256), lds, stream, g, ehat, what, labels, mc, pmax, psum,
                        zt, rmax, rsum, gscale, upstream, dt, ldt, dtt, ldtt, mtiles, ntiles);
     return check_launch("head");
+}
+
+template <typename T, bool FWD>
+static int head_launch(const NtGeom& g, const void* ehat, const void* what, const int* labels, const MarginConstEx& mc, int mk, bool filt,
+                       float* pmax, float* psum, float* zt, const float* rmax, const float* rsum, float gscale,
+                       const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
+#define HEAD_VARIANT(MKV, FV) \
+    if (mk == MKV && filt == FV) \
+        return head_launch_mk<T, FWD, MKV, FV>(g, ehat, what, labels, mc, pmax, psum, zt, rmax, rsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
+    HEAD_VARIANT(MG_ARC, false)
+    HEAD_VARIANT(MG_ARC, true)
+    HEAD_VARIANT(MG_ARC_EASY, false)
+    HEAD_VARIANT(MG_ARC_EASY, true)
+    HEAD_VARIANT(MG_COS, false)
+    HEAD_VARIANT(MG_COS, true)
+#undef HEAD_VARIANT
+    set_error("head: unknown margin variant %d", mk);
+    return FRHIP_EINVAL;
 }
 
 static int head_geom(NtGeom& g, int dtype, int n, int cl, int d, const char* who) {
@@ -335,6 +381,21 @@ static MarginConst margin_const(float s, float m) {
     mc.s = s; mc.cos_m = (float)cos((double)m); mc.sin_m = (float)sin((double)m);
     mc.theta = (float)cos(pi - (double)m); mc.sinmm = (float)(sin(pi - (double)m) * (double)m);
     return mc;
+}
+
+// frhip_margin_t -> (constants, variant); FRHIP_EINVAL for a descriptor the kernels do not implement
+static int margin_desc(const frhip_margin_t* mg, MarginConstEx& mc, int& mk, bool& filt, const char* who) {
+    if (!mg || (mg->kind != FRHIP_MARGIN_ARCFACE && mg->kind != FRHIP_MARGIN_COSFACE) || !(mg->filter_thr >= 0.f)) {
+        set_error("%s: bad margin descriptor (kind=%d thr=%g)", who, mg ? mg->kind : -1, mg ? (double)mg->filter_thr : 0.0);
+        return FRHIP_EINVAL;
+    }
+    const bool arc = mg->kind == FRHIP_MARGIN_ARCFACE;
+    static_cast<MarginConst&>(mc) = margin_const(mg->s, arc ? mg->m : 0.f);
+    mc.m3 = arc ? 0.f : mg->m;
+    mc.thr = mg->filter_thr;
+    mk = arc ? (mg->easy ? MG_ARC_EASY : MG_ARC) : MG_COS;
+    filt = mg->filter_thr > 0.f;
+    return FRHIP_OK;
 }
 
 }  // namespace frhip
@@ -362,19 +423,29 @@ extern "C" int frhip_l2norm_bwd(int dtype, const float* dxhat, const void* xhat,
 
 extern "C" int frhip_head_groups(int num_classes) { return ((num_classes + 127) / 128) * 2; }
 
-extern "C" int frhip_head_fwd(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
-                              int d, float s, float m, float* part_max, float* part_sum, float* ztarget,
-                              float* rowmax, float* rowsum, hipStream_t stream) {
+extern "C" int frhip_head_fwd_ex(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                                 int d, const frhip_margin_t* margin, float* part_max, float* part_sum, float* ztarget,
+                                 float* rowmax, float* rowsum, hipStream_t stream) {
     NtGeom g;
     int rc = head_geom(g, dtype, n, classes, d, "frhip_head_fwd");
     if (rc) return rc;
-    const MarginConst mc = margin_const(s, m);
-    if (dtype == FRHIP_DT_BF16) rc = head_launch<bf16_t, true>(g, ehat, what, labels, mc, part_max, part_sum, ztarget, nullptr, nullptr, 0.f, nullptr, nullptr, 0, nullptr, 0, stream);
-    else rc = head_launch<float, true>(g, ehat, what, labels, mc, part_max, part_sum, ztarget, nullptr, nullptr, 0.f, nullptr, nullptr, 0, nullptr, 0, stream);
+    MarginConstEx mc;
+    int mk;
+    bool filt;
+    if ((rc = margin_desc(margin, mc, mk, filt, "frhip_head_fwd"))) return rc;
+    if (dtype == FRHIP_DT_BF16) rc = head_launch<bf16_t, true>(g, ehat, what, labels, mc, mk, filt, part_max, part_sum, ztarget, nullptr, nullptr, 0.f, nullptr, nullptr, 0, nullptr, 0, stream);
+    else rc = head_launch<float, true>(g, ehat, what, labels, mc, mk, filt, part_max, part_sum, ztarget, nullptr, nullptr, 0.f, nullptr, nullptr, 0, nullptr, 0, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(head_rowreduce_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, part_max, part_sum,
                        frhip_head_groups(classes), n, rowmax, rowsum);
     return check_launch("frhip_head_fwd/rowreduce");
+}
+
+extern "C" int frhip_head_fwd(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                              int d, float s, float m, float* part_max, float* part_sum, float* ztarget,
+                              float* rowmax, float* rowsum, hipStream_t stream) {
+    const frhip_margin_t mg = {FRHIP_MARGIN_ARCFACE, 0, s, m, 0.f};
+    return frhip_head_fwd_ex(dtype, ehat, what, labels, n, classes, d, &mg, part_max, part_sum, ztarget, rowmax, rowsum, stream);
 }
 
 extern "C" int frhip_head_rescale(float* rowsum, const float* local_max, const float* global_max, int n, hipStream_t stream) {
@@ -409,13 +480,23 @@ extern "C" int frhip_head_loss(const float* q, int n, float* loss, hipStream_t s
 extern "C" int frhip_head_bwd_dt(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
                                  int d, float s, float m, const float* rowmax, const float* rowsum, float gscale,
                                  const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
+    const frhip_margin_t mg = {FRHIP_MARGIN_ARCFACE, 0, s, m, 0.f};
+    return frhip_head_bwd_dt_ex(dtype, ehat, what, labels, n, classes, d, &mg, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
+}
+
+extern "C" int frhip_head_bwd_dt_ex(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                                    int d, const frhip_margin_t* margin, const float* rowmax, const float* rowsum, float gscale,
+                                    const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
     NtGeom g;
     int rc = head_geom(g, dtype, n, classes, d, "frhip_head_bwd_dt");
     if (rc) return rc;
     const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
     if (ldt < classes || (ldt % epv)) { set_error("frhip_head_bwd_dt: bad dT pitch %d", ldt); return FRHIP_EINVAL; }
     if (dtt && (ldtt < n || (ldtt % epv))) { set_error("frhip_head_bwd_dt: bad transposed pitch %d", ldtt); return FRHIP_EINVAL; }
-    const MarginConst mc = margin_const(s, m);
-    if (dtype == FRHIP_DT_BF16) return head_launch<bf16_t, false>(g, ehat, what, labels, mc, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
-    return head_launch<float, false>(g, ehat, what, labels, mc, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
+    MarginConstEx mc;
+    int mk;
+    bool filt;
+    if ((rc = margin_desc(margin, mc, mk, filt, "frhip_head_bwd_dt"))) return rc;
+    if (dtype == FRHIP_DT_BF16) return head_launch<bf16_t, false>(g, ehat, what, labels, mc, mk, filt, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
+    return head_launch<float, false>(g, ehat, what, labels, mc, mk, filt, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
 }

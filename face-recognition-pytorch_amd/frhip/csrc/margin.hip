@@ -19,40 +19,56 @@ __device__ __forceinline__ float block_reduce(float v, bool is_max, float* red) 
     return r;
 }
 
-// out = s * margin(logits): kind 0 = ArcFace (cos(theta+m), fallback t - m sin(pi-m) below cos(pi-m)), 1 = CosFace (t - m).
+// out = s * margin(logits): kind 0 = ArcFace (cos(theta+m), fallback t - m sin(pi-m) below cos(pi-m); easy: cos(theta+m) for
+// t > 0, else t), 1 = CosFace (t - m).  thr > 0: interclass filtering -- a non-target element > thr becomes 0 and its bit is set
+// in filt (one 64-bit word per 64 columns, written by lane 0 of the wave that covers them).
 // tsave[row] keeps the raw target cosine for the backward slope.  In place on `logits`.
 __global__ __launch_bounds__(256) void margin_fwd_kernel(float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                          int C, float s, float cos_m, float sin_m, float theta,
-                                                         float sinmm, float m3, int kind, float* __restrict__ tsave) {
+                                                         float sinmm, float m3, int kind, float* __restrict__ tsave,
+                                                         int easy, float thr, uint64_t* __restrict__ filt) {
     const int row = blockIdx.x;
     float* x = logits + (size_t)row * C;
     const int64_t lab = labels[row];
+    const int words = (C + 63) / 64;
     for (int j = threadIdx.x; j < C; j += 256) {
         float t = x[j];
+        bool dirty = false;
         if (j == lab) {
             tsave[row] = t;
             if (kind == 0) {
                 const float sin_t = sqrtf(1.f - t * t);
-                t = t > theta ? t * cos_m - sin_t * sin_m : t - sinmm;
+                if (easy) t = t > 0.f ? t * cos_m - sin_t * sin_m : t;
+                else t = t > theta ? t * cos_m - sin_t * sin_m : t - sinmm;
             } else {
                 t = t - m3;
             }
+        } else if (thr > 0.f && t > thr) {
+            t = 0.f;
+            dirty = true;
         }
         x[j] = t * s;
+        if (filt) {
+            const uint64_t bits = __ballot(dirty);
+            if ((threadIdx.x & 63) == 0) filt[(size_t)row * words + j / 64] = bits;
+        }
     }
 }
 
 __global__ __launch_bounds__(256) void margin_bwd_kernel(const float* __restrict__ gout, const int64_t* __restrict__ labels,
                                                          const float* __restrict__ tsave, int C, float s, float cos_m,
-                                                         float sin_m, float theta, int kind, float* __restrict__ gin) {
+                                                         float sin_m, float theta, int kind, float* __restrict__ gin,
+                                                         int easy, const uint64_t* __restrict__ filt) {
     const int row = blockIdx.x;
     const int64_t lab = labels[row];
+    const int words = (C + 63) / 64;
     for (int j = threadIdx.x; j < C; j += 256) {
         float gg = gout[(size_t)row * C + j] * s;
         if (j == lab && kind == 0) {
             const float t = tsave[row];
-            if (t > theta) gg *= cos_m + t * sin_m / sqrtf(1.f - t * t);
+            if (t > (easy ? 0.f : theta)) gg *= cos_m + t * sin_m / sqrtf(1.f - t * t);
         }
+        if (filt && ((filt[(size_t)row * words + j / 64] >> (j & 63)) & 1)) gg = 0.f;
         gin[(size_t)row * C + j] = gg;
     }
 }
@@ -105,20 +121,45 @@ __global__ __launch_bounds__(256) void ce_grad_kernel(float* __restrict__ p, int
 
 using namespace frhip;
 
+extern "C" int frhip_margin_fwd_ex(float* logits, const int64_t* labels, int n, int c, const frhip_margin_t* margin, float* tsave,
+                                   uint64_t* filtered, hipStream_t stream) {
+    if (!margin || (margin->kind != FRHIP_MARGIN_ARCFACE && margin->kind != FRHIP_MARGIN_COSFACE) || !(margin->filter_thr >= 0.f) ||
+        (margin->filter_thr > 0.f && !filtered)) {
+        set_error("frhip_margin_fwd: bad margin descriptor or missing filter mask");
+        return FRHIP_EINVAL;
+    }
+    if (n <= 0) return FRHIP_OK;
+    const double pi = 3.14159265358979323846, m = margin->m;
+    hipLaunchKernelGGL(margin_fwd_kernel, dim3(n), dim3(256), 0, stream, logits, labels, c, margin->s, (float)cos(m), (float)sin(m),
+                       (float)cos(pi - m), (float)(sin(pi - m) * m), margin->m, margin->kind, tsave, margin->easy,
+                       margin->filter_thr, margin->filter_thr > 0.f ? filtered : nullptr);
+    return check_launch("frhip_margin_fwd");
+}
+
+extern "C" int frhip_margin_bwd_ex(const float* gout, const int64_t* labels, const float* tsave, const uint64_t* filtered, int n, int c,
+                                   const frhip_margin_t* margin, float* gin, hipStream_t stream) {
+    if (!margin || (margin->kind != FRHIP_MARGIN_ARCFACE && margin->kind != FRHIP_MARGIN_COSFACE) || !(margin->filter_thr >= 0.f) ||
+        (margin->filter_thr > 0.f && !filtered)) {
+        set_error("frhip_margin_bwd: bad margin descriptor or missing filter mask");
+        return FRHIP_EINVAL;
+    }
+    if (n <= 0) return FRHIP_OK;
+    const double pi = 3.14159265358979323846, m = margin->m;
+    hipLaunchKernelGGL(margin_bwd_kernel, dim3(n), dim3(256), 0, stream, gout, labels, tsave, c, margin->s, (float)cos(m), (float)sin(m),
+                       (float)cos(pi - m), margin->kind, gin, margin->easy, margin->filter_thr > 0.f ? filtered : nullptr);
+    return check_launch("frhip_margin_bwd");
+}
+
 extern "C" int frhip_margin_fwd(float* logits, const int64_t* labels, int n, int c, float s, float m, int kind,
                                 float* tsave, hipStream_t stream) {
-    const double pi = 3.14159265358979323846;
-    hipLaunchKernelGGL(margin_fwd_kernel, dim3(n), dim3(256), 0, stream, logits, labels, c, s, (float)cos((double)m),
-                       (float)sin((double)m), (float)cos(pi - (double)m), (float)(sin(pi - (double)m) * (double)m), m, kind, tsave);
-    return check_launch("frhip_margin_fwd");
+    const frhip_margin_t mg = {kind, 0, s, m, 0.f};
+    return frhip_margin_fwd_ex(logits, labels, n, c, &mg, tsave, nullptr, stream);
 }
 
 extern "C" int frhip_margin_bwd(const float* gout, const int64_t* labels, const float* tsave, int n, int c, float s,
                                 float m, int kind, float* gin, hipStream_t stream) {
-    const double pi = 3.14159265358979323846;
-    hipLaunchKernelGGL(margin_bwd_kernel, dim3(n), dim3(256), 0, stream, gout, labels, tsave, c, s, (float)cos((double)m),
-                       (float)sin((double)m), (float)cos(pi - (double)m), kind, gin);
-    return check_launch("frhip_margin_bwd");
+    const frhip_margin_t mg = {kind, 0, s, m, 0.f};
+    return frhip_margin_bwd_ex(gout, labels, tsave, nullptr, n, c, &mg, gin, stream);
 }
 
 extern "C" int frhip_rows_max(const float* x, int n, int c, float* rowmax, hipStream_t stream) {

@@ -679,7 +679,22 @@ def head_dw(dt, ehat, what, wnorm, out_scale=1.0):
     return dw
 
 
-def head_fwd(ehat, what, labels_i32, s, m):
+MARGIN_ARCFACE, MARGIN_COSFACE = 0, 1          # frhip_margin_t.kind
+
+
+class _MarginDesc(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("easy", ctypes.c_int), ("s", ctypes.c_float), ("m", ctypes.c_float),
+                ("filter_thr", ctypes.c_float)]
+
+
+def _margin_desc(margin):
+    """margin: (kind, easy, s, m, filter_thr), e.g. nets.ArcFace.Margin -> frhip_margin_t (passed by pointer)"""
+    kind, easy, s, m, thr = margin
+    return _MarginDesc(int(kind), int(bool(easy)), float(s), float(m), float(thr))
+
+
+def head_fwd(ehat, what, labels_i32, s, m, margin=None):
+    """margin=None: ArcFace(s, m) (frhip_head_fwd); else a (kind, easy, s, m, filter_thr) descriptor (frhip_head_fwd_ex)"""
     n, d = ehat.shape
     classes = what.shape[0]
     groups = lib().frhip_head_groups(classes)
@@ -689,8 +704,13 @@ def head_fwd(ehat, what, labels_i32, s, m):
     zt = torch.zeros((n,), dtype=torch.float32, device=dev)
     rmax = torch.empty((n,), dtype=torch.float32, device=dev)
     rsum = torch.empty((n,), dtype=torch.float32, device=dev)
-    check(lib().frhip_head_fwd(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, s, m, _p(pm), _p(ps),
-                               _p(zt), _p(rmax), _p(rsum), _s()), "frhip_head_fwd")
+    if margin is None:
+        check(lib().frhip_head_fwd(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, s, m, _p(pm), _p(ps),
+                                   _p(zt), _p(rmax), _p(rsum), _s()), "frhip_head_fwd")
+    else:
+        desc = _margin_desc(margin)
+        check(lib().frhip_head_fwd_ex(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, ctypes.byref(desc), _p(pm),
+                                      _p(ps), _p(zt), _p(rmax), _p(rsum), _s()), "frhip_head_fwd_ex")
     return zt, rmax, rsum
 
 
@@ -727,8 +747,9 @@ def head_loss(q):
     return loss
 
 
-def head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, gscale, upstream=None, transposed=False):
-    """dT [n][classes padded]; transposed=True: also dTt [classes][n padded] from the same launch -> (dT, dTt)"""
+def head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, gscale, upstream=None, transposed=False, margin=None):
+    """dT [n][classes padded]; transposed=True: also dTt [classes][n padded] from the same launch -> (dT, dTt).
+    margin: as in head_fwd"""
     n, d = ehat.shape
     classes = what.shape[0]
     e = epv(ehat.dtype)
@@ -738,8 +759,13 @@ def head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, gscale, upstream=None,
     if transposed:
         ldtt = (n + e - 1) // e * e
         dtt = torch.empty((classes, ldtt), dtype=ehat.dtype, device=ehat.device)
-    check(lib().frhip_head_bwd_dt(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, s, m, _p(rmax),
-                                  _p(rsum), gscale, _p(upstream), _p(dt), ldt, _p(dtt), ldtt, _s()), "frhip_head_bwd_dt")
+    if margin is None:
+        check(lib().frhip_head_bwd_dt(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, s, m, _p(rmax),
+                                      _p(rsum), gscale, _p(upstream), _p(dt), ldt, _p(dtt), ldtt, _s()), "frhip_head_bwd_dt")
+    else:
+        desc = _margin_desc(margin)
+        check(lib().frhip_head_bwd_dt_ex(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, ctypes.byref(desc), _p(rmax),
+                                         _p(rsum), gscale, _p(upstream), _p(dt), ldt, _p(dtt), ldtt, _s()), "frhip_head_bwd_dt_ex")
     return (dt, dtt) if transposed else dt
 
 
@@ -755,6 +781,25 @@ def margin_bwd(gout, labels_i64, tsave, s, m, kind):
     n, c = gout.shape
     gin = torch.empty_like(gout)
     check(lib().frhip_margin_bwd(_p(gout), _p(labels_i64), _p(tsave), n, c, s, m, kind, _p(gin), _s()), "frhip_margin_bwd")
+    return gin
+
+
+def margin_fwd_ex(logits, labels_i64, margin):
+    """in place on logits [n, c] fp32 with a (kind, easy, s, m, filter_thr) descriptor -> (tsave, filter mask or None)"""
+    n, c = logits.shape
+    desc = _margin_desc(margin)
+    tsave = torch.zeros((n,), dtype=torch.float32, device=logits.device)
+    filt = torch.empty((n, (c + 63) // 64), dtype=torch.int64, device=logits.device) if desc.filter_thr > 0 else None
+    check(lib().frhip_margin_fwd_ex(_p(logits), _p(labels_i64), n, c, ctypes.byref(desc), _p(tsave), _p(filt), _s()), "frhip_margin_fwd_ex")
+    return tsave, filt
+
+
+def margin_bwd_ex(gout, labels_i64, tsave, filt, margin):
+    n, c = gout.shape
+    desc = _margin_desc(margin)
+    gin = torch.empty_like(gout)
+    check(lib().frhip_margin_bwd_ex(_p(gout), _p(labels_i64), _p(tsave), _p(filt), n, c, ctypes.byref(desc), _p(gin), _s()),
+          "frhip_margin_bwd_ex")
     return gin
 
 

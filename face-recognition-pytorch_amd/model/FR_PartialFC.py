@@ -75,10 +75,13 @@ class Model(nn.Module):
                 else:
                     self.encoder = DDP(self.encoder, broadcast_buffers=False, device_ids=[conf.local_rank])
             head_mod = importlib.import_module("nets.%s" % getattr(conf, "loss", "PartialFC"))
+            # conf.margin_loss (optional, not in the reference): a callable (s, m) -> margin module, e.g. nets.ArcFace.CosFace;
+            # absent = the reference's ArcFace
+            margin = {"margin_loss": conf.margin_loss} if getattr(conf, "margin_loss", None) is not None else {}
             if conf.optimizer == "SGD":
-                self.loss = head_mod.PartialFC(conf=conf, num_classes=conf.n_classes)
+                self.loss = head_mod.PartialFC(conf=conf, num_classes=conf.n_classes, **margin)
             elif conf.optimizer == "AdamW":
-                self.loss = head_mod.PartialFCAdamW(conf=conf, num_classes=conf.n_classes)
+                self.loss = head_mod.PartialFCAdamW(conf=conf, num_classes=conf.n_classes, **margin)
             else:
                 raise ValueError(conf.optimizer)
             self.loss.train().to(conf.local_rank)

@@ -11,7 +11,7 @@ What runs where
     [num_local] vectors; the uniform draws come from torch's CPU generator exactly like the reference (:110), so
     `weight_index` is reproducible from the CPU seed alone;
   * everything floating-point is libfrhip: row l2-normalise, ONE fused kernel for cos-theta GEMM -> clamp ->
-    ArcFace margin -> x s -> per-row max / sum-exp (logits never reach HBM), a recompute kernel that emits
+    margin (ArcFace; CosFace, easy margin, interclass filtering as kernel variants) -> x s -> per-row max / sum-exp (logits never reach HBM), a recompute kernel that emits
     d loss / d cos once, two MFMA TN GEMMs for dW and dE, normalise-backward, and row gather / scatter of the
     sampled class centres;
   * cross-rank traffic is torch.distributed (backend "nccl" = RCCL over xGMI), FOUR collectives per step on
@@ -30,7 +30,7 @@ from typing import Callable
 import torch
 from torch import distributed
 
-from .ArcFace import ArcFace
+from .ArcFace import SUPPORTED as SUPPORTED_MARGINS, ArcFace, CombinedMarginLoss, CosFace, is_plain_arcface, margin_of
 
 
 import os
@@ -54,8 +54,9 @@ class HipHeadKernels:
     def normalize(self, x):
         return self.ops.l2norm_rows(x.contiguous(), self.dtype)          # (xhat, norms)
 
-    def forward_stats(self, ehat, what, labels_i32, s, m):
-        return self.ops.head_fwd(ehat, what, labels_i32, s, m)           # (ztarget, rowmax, rowsum) of this shard
+    def forward_stats(self, ehat, what, labels_i32, s, m, margin=None):
+        """margin: None = ArcFace(s, m); else a nets.ArcFace.Margin (CosFace, easy margin, interclass filtering)"""
+        return self.ops.head_fwd(ehat, what, labels_i32, s, m, margin=margin)     # (ztarget, rowmax, rowsum) of this shard
 
     def rescale(self, rowsum, local_max, global_max):
         self.ops.head_rescale(rowsum, local_max, global_max)
@@ -72,14 +73,15 @@ class HipHeadKernels:
     def merge_stats(self, gathered):
         return self.ops.head_merge_stats(gathered)                         # global (rowmax, rowsum, q)
 
-    def backward(self, ehat, enorm, what, wnorm, labels_i32, s, m, rmax, rsum, n_global, upstream, e_scale=1.0, on_de=None):
-        """-> (d_emb * e_scale, d_weight).  on_de(d_emb) is called as soon as the embedding gradient is enqueued, before the
+    def backward(self, ehat, enorm, what, wnorm, labels_i32, s, m, rmax, rsum, n_global, upstream, e_scale=1.0, on_de=None,
+                 margin=None):
+        """-> (d_emb * e_scale, d_weight).  margin: as in forward_stats.  on_de(d_emb) is called as soon as the embedding gradient is enqueued, before the
         weight-gradient GEMM: the caller starts the cross-rank reduce-scatter there and the two overlap."""
         ops = self.ops
         n, d = ehat.shape
         classes = what.shape[0]
         # dT and its transpose from ONE launch (the embedding gradient contracts over classes, the weight gradient over samples)
-        dt, dtt = ops.head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, 1.0 / n_global, upstream, transposed=True)
+        dt, dtt = ops.head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, 1.0 / n_global, upstream, transposed=True, margin=margin)
         d_eh = torch.zeros((n, d), dtype=torch.float32, device=ehat.device)
         ops.gemm_tn(dtt, what, d_eh, kc=n)
         d_e = ops.l2norm_bwd(d_eh, ehat, enorm, out_scale=e_scale)
@@ -162,7 +164,7 @@ class _MarginSoftmaxFn(torch.autograd.Function):
     Arithmetic: SURVEY.md Appendix A steps 1-7 (nets/PartialFC.py:182, :198-207, nets/ArcFace.py:76-91, :441-484, :504-522)."""
 
     @staticmethod
-    def forward(ctx, local_embeddings, weight_activated, labels_i32, kern, s, m, world_size, collectives):
+    def forward(ctx, local_embeddings, weight_activated, labels_i32, kern, s, m, world_size, collectives, margin=None):
         local_embeddings = local_embeddings.contiguous()
         rows, dim = local_embeddings.shape
         if collectives:                                                         # :182 (C1)
@@ -171,7 +173,9 @@ class _MarginSoftmaxFn(torch.autograd.Function):
             embeddings = local_embeddings
         ehat, enorm = kern.normalize(embeddings)
         what, wnorm = kern.normalize(weight_activated)
-        zt, rmax, rsum = kern.forward_stats(ehat, what, labels_i32, s, m)
+        # margin None (ArcFace, the reference default): the kernel interface is called exactly as before the other margins existed
+        extra = {} if margin is None else {"margin": margin}
+        zt, rmax, rsum = kern.forward_stats(ehat, what, labels_i32, s, m, **extra)
         if collectives:                                                         # :448, :453, :459 (C3-C5) in one exchange
             mine = kern.pack_stats(zt, labels_i32, rmax, rsum)
             allst = _all_gather_flat(mine.new_empty((world_size * mine.shape[0], mine.shape[1])), mine)
@@ -180,6 +184,7 @@ class _MarginSoftmaxFn(torch.autograd.Function):
             q = kern.target_prob(zt, labels_i32, rmax, rsum)
         loss = kern.loss(q)
         ctx.kern, ctx.s, ctx.m, ctx.world_size, ctx.collectives, ctx.rows = kern, s, m, world_size, collectives, rows
+        ctx.extra = extra
         ctx.save_for_backward(ehat, enorm, what, wnorm, labels_i32, rmax, rsum)
         return loss.reshape(())
 
@@ -188,8 +193,8 @@ class _MarginSoftmaxFn(torch.autograd.Function):
         ehat, enorm, what, wnorm, labels_i32, rmax, rsum = ctx.saved_tensors
         up = grad_loss.reshape(1).float().contiguous()
         if not ctx.collectives:
-            d_e, d_w = ctx.kern.backward(ehat, enorm, what, wnorm, labels_i32, ctx.s, ctx.m, rmax, rsum, ehat.shape[0], up)
-            return d_e, d_w, None, None, None, None, None, None
+            d_e, d_w = ctx.kern.backward(ehat, enorm, what, wnorm, labels_i32, ctx.s, ctx.m, rmax, rsum, ehat.shape[0], up, **ctx.extra)
+            return d_e, d_w, None, None, None, None, None, None, None
         # :504-522 (C6): reduce-scatter(SUM) of dE, x world_size (folded into the normalise-backward's scale); issued as soon
         # as dE is enqueued so that it runs beside the dW GEMM
         pending = []
@@ -199,11 +204,11 @@ class _MarginSoftmaxFn(torch.autograd.Function):
             pending.append(_reduce_scatter_sum(d_e, rank, ctx.rows, async_op=True))
 
         _, d_w = ctx.kern.backward(ehat, enorm, what, wnorm, labels_i32, ctx.s, ctx.m, rmax, rsum, ehat.shape[0], up,
-                                   e_scale=float(ctx.world_size), on_de=start)
+                                   e_scale=float(ctx.world_size), on_de=start, **ctx.extra)
         d_local, work = pending[0]
         if work is not None:
             work.wait()
-        return d_local, d_w, None, None, None, None, None, None
+        return d_local, d_w, None, None, None, None, None, None, None
 
 
 class DistCrossEntropyFunc(torch.autograd.Function):
@@ -279,8 +284,9 @@ class _PartialFCBase(torch.nn.Module):
             self.margin_softmax = margin_loss(conf.loss_s, conf.loss_m)
         else:
             raise
-        if getattr(self.margin_softmax, "kind", None) != "arcface":
-            raise NotImplementedError("the fused head kernel implements the ArcFace margin (the reference default)")
+        if not isinstance(self.margin_softmax, (ArcFace, CosFace, CombinedMarginLoss)):
+            raise NotImplementedError("the fused head kernel implements the margin modules %s, not %s"
+                                      % (SUPPORTED_MARGINS, type(self.margin_softmax).__name__))
         self._kernels = kernels
         self._conf = conf
         self.step = 0
@@ -497,10 +503,14 @@ class _PartialFCBase(torch.nn.Module):
             "last batch size do not equal current batch size: {} vs {}".format(self.last_batch_size, batch_size))
         collectives = self.world_size > 1 or _FORCE_COLLECTIVES
         n_global = batch_size * self.world_size
-        s, m = float(self.margin_softmax.scale), float(self.margin_softmax.margin)
+        # the margin is read from the module at every call: a later `margin_softmax.easy_margin = True` takes effect, as in the
+        # reference; plain ArcFace goes down the head's original interface (margin None)
+        mg = margin_of(self.margin_softmax)
+        s, m = mg.s, mg.m
+        margin = None if is_plain_arcface(mg) else mg
         if ready is not None and ready.numel() == n_global:      # everything label-side was done by prepare()
             return _MarginSoftmaxFn.apply(local_embeddings, self.weight_activated, ready, self.kernels, s, m,
-                                          self.world_size, collectives)
+                                          self.world_size, collectives, margin)
         n_pos = None
         if prep is not None and prep[1].numel() == n_global:
             labels, n_pos = prep[1], prep[2]                      # gathered at the start of the step by prepare()
@@ -516,7 +526,7 @@ class _PartialFCBase(torch.nn.Module):
         if self.sample_rate < 1:
             self.sample(labels, index_positive, optimizer, n_pos)
         return _MarginSoftmaxFn.apply(local_embeddings, self.weight_activated, labels.view(-1).to(torch.int32).contiguous(),
-                                      self.kernels, s, m, self.world_size, collectives)
+                                      self.kernels, s, m, self.world_size, collectives, margin)
 
     def arm_early_update(self, optimizer):
         """Call between forward() and loss.backward() of a step whose gradient clip leaves the class centres out and that calls

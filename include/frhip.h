@@ -276,6 +276,27 @@ int frhip_head_bwd_dt(int dtype, const void* ehat, const void* what, const int* 
                       int d, float s, float m, const float* rowmax, const float* rowsum, float gscale,
                       const float* upstream, void* dt, int ldt, void* dtt, int ldtt, frhip_stream_t stream);
 
+/* Margin descriptor of the fused head and the explicit-logit margin (the three modules of the reference's nets/ArcFace.py):
+ *   kind FRHIP_MARGIN_ARCFACE, easy 0: ArcFace(s, m) / CombinedMarginLoss(s, 1, m, 0) -- target t -> cos(theta + m) above cos(pi - m),
+ *                                      else t - m sin(pi - m) (nets/ArcFace.py:76-91, :41-51)
+ *   kind FRHIP_MARGIN_ARCFACE, easy 1: the easy_margin switch -- target t -> cos(theta + m) for t > 0, else t (:45-47, :82-84)
+ *   kind FRHIP_MARGIN_COSFACE:         CosFace(s, m) / CombinedMarginLoss(s, *, *, m3 = m) -- target t -> t - m (:53-57, :94-106)
+ *   filter_thr > 0:                    interclass_filtering_threshold (:28-39): every element that is not its row's target and whose
+ *                                      (clamped) cosine is > filter_thr becomes 0 (logit 0, gradient 0); a row whose label is -1 on this
+ *                                      shard has no exempt column.  0 = off.
+ * Every logit is then x s. */
+#define FRHIP_MARGIN_ARCFACE 0
+#define FRHIP_MARGIN_COSFACE 1
+typedef struct { int kind; int easy; float s, m, filter_thr; } frhip_margin_t;
+/* frhip_head_fwd / frhip_head_bwd_dt with any margin descriptor (nets/PartialFC.py:198-207 with margin_loss = any module of
+ * nets/ArcFace.py).  A plain ArcFace descriptor (easy 0, filter_thr 0) runs exactly the kernels of frhip_head_fwd / _bwd_dt. */
+int frhip_head_fwd_ex(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                      int d, const frhip_margin_t* margin, float* part_max, float* part_sum, float* ztarget,
+                      float* rowmax, float* rowsum, frhip_stream_t stream);
+int frhip_head_bwd_dt_ex(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                         int d, const frhip_margin_t* margin, const float* rowmax, const float* rowsum, float gscale,
+                         const float* upstream, void* dt, int ldt, void* dtt, int ldtt, frhip_stream_t stream);
+
 /* ---- bn1 -> relu -> conv2 of a BasicBlock (nets/resnet.py:91-93) WITHOUT the activated tensor: the BatchNorm-apply + ReLU
  * is folded into the operand path of the convolution (forward) and of its weight gradient, which read the saved BatchNorm
  * INPUT x and form relu(x * in_scale[c] + in_shift[c]) in LDS.  bf16, 3x3 / stride 1 / pad 1; *_fusable() tells whether a
@@ -356,6 +377,14 @@ int frhip_margin_fwd(float* logits, const int64_t* labels, int n, int c, float s
                      frhip_stream_t stream);
 int frhip_margin_bwd(const float* gout, const int64_t* labels, const float* tsave, int n, int c, float s, float m,
                      int kind, float* gin, frhip_stream_t stream);
+/* the same with a margin descriptor (frhip_margin_t above): CombinedMarginLoss.forward with interclass filtering
+ * (nets/ArcFace.py:28-39) and the easy_margin switch (:45-47, :82-84).  filtered[n][(c + 63) / 64] (may be NULL when
+ * filter_thr == 0): bit j % 64 of word j / 64 of a row is set where element j was filtered; the forward writes it, the backward
+ * reads it (logits are overwritten in place, so the mask cannot be recomputed from them). */
+int frhip_margin_fwd_ex(float* logits, const int64_t* labels, int n, int c, const frhip_margin_t* margin, float* tsave,
+                        uint64_t* filtered, frhip_stream_t stream);
+int frhip_margin_bwd_ex(const float* gout, const int64_t* labels, const float* tsave, const uint64_t* filtered, int n, int c,
+                        const frhip_margin_t* margin, float* gin, frhip_stream_t stream);
 int frhip_rows_max(const float* x, int n, int c, float* rowmax, frhip_stream_t stream);
 int frhip_rows_exp_sum(float* x, int n, int c, const float* rowmax, float* rowsum, frhip_stream_t stream);
 int frhip_rows_normalize(float* x, int n, int c, const float* rowsum, const int64_t* labels, float* ptarget,
