@@ -25,6 +25,8 @@ def _ctype(decl):
         return ctypes.c_void_p
     if base == "int":
         return ctypes.c_int
+    if base == "int64_t":
+        return ctypes.c_int64
     if d.startswith("long long"):
         return ctypes.c_longlong
     if base == "float":

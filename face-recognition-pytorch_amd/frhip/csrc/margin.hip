@@ -206,6 +206,28 @@ __global__ void pair_score_kernel(const float* __restrict__ e1, const float* __r
     if (idx >= 0 && idx <= 100000) atomicAdd(labels[i] ? hist_genuine + idx : hist_imposter + idx, 1);
 }
 
+// ---- cross-matching per-pair arithmetic, shared by cross_score_kernel (pair list) and cross_hist_kernel (histograms only) so the
+// two cannot drift apart.  sum += (double)(float)(e[j][k] - e[i][k])^2 in ascending k: the square of a float is exact in double
+// (48 significant bits fit in 53), so a fused or a separate multiply-add give the same sum and only the order of the adds matters.
+__device__ __forceinline__ double cross_acc(double sum, float ej, float ei) {
+    const double dd = (double)(ej - ei);
+    return sum + dd * dd;
+}
+__device__ __forceinline__ double cross_pair_score(double sum) { return 1.0 - sum / 4.0; }
+// the reference's bin int(99999 * score); counted only when it lands in [0, 100000]
+__device__ __forceinline__ int cross_bin(double score) { return (int)((1e5 - 1.0) * score); }
+// threshold slot: the smallest t in [0, 100001] with score <= t / 1e5, where t / 1e5 is the correctly rounded double quotient that
+// Python's `th / 1e5` computes (scores <= 0 go to slot 0, scores > 1 to slot 100001, above every threshold th <= 100000).  Then
+// "score <= th / 1e5" holds exactly for the pairs of slots t <= th.  NaN (no compare holds for it): -1, counted nowhere.
+__device__ __forceinline__ int cross_thr_slot(double score) {
+    if (!(score > 0.0)) return score <= 0.0 ? 0 : -1;
+    if (score > 1.0) return 100001;
+    int t = (int)ceil(score * 1e5);                      // within 1 of the answer: the product is off by at most an ulp
+    while (t > 0 && score <= (double)(t - 1) / 1e5) --t;
+    while (t < 100000 && !(score <= (double)t / 1e5)) ++t;
+    return t;
+}
+
 // ---- cross-matching scores (/root/reference/utils/eval.py:102-137): every unordered pair (j < i) of one embedding set, in
 // the reference's order l = i (i - 1) / 2 + j; same float64-of-float32-differences arithmetic as pair_score, label 1 where
 // the identities agree.  One thread per pair, 16 x 16 pairs per block.
@@ -216,19 +238,79 @@ __global__ __launch_bounds__(256) void cross_score_kernel(const float* __restric
     const int i = blockIdx.y * 16 + (threadIdx.x >> 4), j = blockIdx.x * 16 + (threadIdx.x & 15);
     if (i >= n || j >= i) return;
     double sum = 0.0;
-    for (int k = 0; k < d; ++k) {
-        const float df = e[(size_t)j * d + k] - e[(size_t)i * d + k];
-        const double dd = (double)df;
-        sum += dd * dd;
-    }
-    const double score = 1.0 - sum / 4.0;
-    const int idx = (int)((1e5 - 1.0) * score);
+    for (int k = 0; k < d; ++k) sum = cross_acc(sum, e[(size_t)j * d + k], e[(size_t)i * d + k]);
+    const double score = cross_pair_score(sum);
+    const int idx = cross_bin(score);
     const size_t l = (size_t)i * (i - 1) / 2 + j;
     const bool genuine = labels[j] == labels[i];
     scores[l] = score;
     pair_labels[l] = genuine ? 1.0 : 0.0;
     hist_idx[l] = idx;
     if (idx >= 0 && idx <= 100000) atomicAdd(genuine ? hist_genuine + idx : hist_imposter + idx, 1);
+}
+
+// ---- cross-matching histograms without the pair list: the pairs (i, j < i) with i in a band [i0, i1) add into four uint64
+// histograms (reference bins and threshold slots, genuine / imposter).  Tiles of 128 x 128 pairs, 256 threads, each thread an
+// 8 x 8 register tile of float64 sums; row slices of both blocks are staged through LDS in K-chunks of 32, [k][row] so that one
+// thread's 8 rows at one k are two ds_read_b128.  Columns k >= d are zero on both sides and add exactly 0.  No MFMA: its internal
+// order of sums is not the sequential one.
+constexpr int CH_T = 128, CH_KC = 32, CH_LD = CH_T + 4;
+
+__device__ __forceinline__ void hist_add(unsigned long long* h, int k) {
+    __hip_atomic_fetch_add(h + k, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(256, 2) void cross_hist_kernel(const float* __restrict__ e, const int64_t* __restrict__ labels, int64_t n,
+                                                            int d, int64_t i0, int64_t i1, unsigned long long* __restrict__ hg,
+                                                            unsigned long long* __restrict__ hi, unsigned long long* __restrict__ tg,
+                                                            unsigned long long* __restrict__ ti) {
+    __shared__ __attribute__((aligned(16))) float li[CH_KC][CH_LD], lj[CH_KC][CH_LD];
+    const int64_t ib = i0 + (int64_t)blockIdx.y * CH_T, jb = (int64_t)blockIdx.x * CH_T;
+    const int64_t iend = ib + CH_T < i1 ? ib + CH_T : i1;
+    if (jb >= iend - 1) return;                          // no j < i in this tile (block-uniform, before any barrier)
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    double acc[8][8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) acc[a][b] = 0.0;
+    for (int k0 = 0; k0 < d; k0 += CH_KC) {
+        __syncthreads();
+        for (int m = threadIdx.x; m < CH_T * CH_KC; m += 256) {
+            const int r = m / CH_KC, kk = m % CH_KC, k = k0 + kk;
+            const int64_t gi = ib + r, gj = jb + r;      // both < iend <= n when loaded
+            li[kk][r] = (gi < iend && k < d) ? e[gi * d + k] : 0.f;
+            lj[kk][r] = (gj < iend && k < d) ? e[gj * d + k] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int kk = 0; kk < CH_KC; ++kk) {
+            const f32x4_t a0 = *(const f32x4_t*)&li[kk][ty * 8], a1 = *(const f32x4_t*)&li[kk][ty * 8 + 4];
+            const f32x4_t b0 = *(const f32x4_t*)&lj[kk][tx * 8], b1 = *(const f32x4_t*)&lj[kk][tx * 8 + 4];
+            const float ai[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+            const float bj[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
+#pragma unroll
+            for (int a = 0; a < 8; ++a)
+#pragma unroll
+                for (int b = 0; b < 8; ++b) acc[a][b] = cross_acc(acc[a][b], bj[b], ai[a]);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+        const int64_t i = ib + ty * 8 + a;
+        if (i >= iend) continue;
+        const int64_t lab = labels[i];
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const int64_t j = jb + tx * 8 + b;
+            if (j >= i) continue;
+            const double score = cross_pair_score(acc[a][b]);
+            const bool genuine = labels[j] == lab;
+            const int idx = cross_bin(score), t = cross_thr_slot(score);
+            if (idx >= 0 && idx <= 100000) hist_add(genuine ? hg : hi, idx);
+            if (t >= 0) hist_add(genuine ? tg : ti, t);
+        }
+    }
 }
 }  // namespace frhip
 
@@ -248,4 +330,31 @@ extern "C" int frhip_cross_score(const float* e, const int64_t* labels, int n, i
     hipLaunchKernelGGL(frhip::cross_score_kernel, dim3(t, t), dim3(256), 0, stream, e, labels, n, d, scores, pair_labels,
                        hist_idx, hist_genuine, hist_imposter);
     return frhip::check_launch("frhip_cross_score");
+}
+
+extern "C" int frhip_cross_hist(const float* e, const int64_t* labels, int64_t n, int d, int64_t i0, int64_t i1, uint64_t* hist_genuine,
+                                uint64_t* hist_imposter, uint64_t* thr_genuine, uint64_t* thr_imposter, hipStream_t stream) {
+    if (n < 0 || d <= 0 || i0 < 0 || i1 > n || i0 > i1) {
+        frhip::set_error("frhip_cross_hist: bad arguments n = %lld, d = %d, band [%lld, %lld)", (long long)n, d, (long long)i0,
+                         (long long)i1);
+        return FRHIP_EINVAL;
+    }
+    if (i1 < 2 || i0 == i1) return FRHIP_OK;             // no pair j < i in the band
+    if (!e || !labels || !hist_genuine || !hist_imposter || !thr_genuine || !thr_imposter) {
+        frhip::set_error("frhip_cross_hist: null pointer");
+        return FRHIP_EINVAL;
+    }
+    using frhip::CH_T;
+    const int64_t cols = (i1 - 2) / CH_T + 1;           // column tiles up to the last j = i1 - 2
+    if (cols > 0x7fffffff / 256) { frhip::set_error("frhip_cross_hist: n = %lld too large", (long long)n); return FRHIP_EINVAL; }
+    // grid.y is capped at 65535: taller bands go as several launches of at most 65535 row tiles
+    for (int64_t r0 = i0; r0 < i1; r0 += (int64_t)65535 * CH_T) {
+        const int64_t r1 = r0 + (int64_t)65535 * CH_T < i1 ? r0 + (int64_t)65535 * CH_T : i1;
+        hipLaunchKernelGGL(frhip::cross_hist_kernel, dim3((unsigned)cols, (unsigned)((r1 - r0 + CH_T - 1) / CH_T)), dim3(256), 0, stream,
+                           e, labels, n, d, r0, r1, (unsigned long long*)hist_genuine, (unsigned long long*)hist_imposter,
+                           (unsigned long long*)thr_genuine, (unsigned long long*)thr_imposter);
+        const int rc = frhip::check_launch("frhip_cross_hist");
+        if (rc) return rc;
+    }
+    return FRHIP_OK;
 }

@@ -1,4 +1,5 @@
 """Tensor-level wrappers over the C ABI (torch is used for device memory + the current HIP stream only)."""
+import math
 import weakref
 
 import ctypes
@@ -909,6 +910,39 @@ def cross_score(e, labels_i64):
     check(lib().frhip_cross_score(_p(e), _p(labels_i64), n, d, _p(scores), _p(plab), _p(idx), _p(hg), _p(hi), _s()),
           "frhip_cross_score")
     return scores, plab, idx, hg, hi
+
+
+CROSS_HIST_PAIRS_PER_LAUNCH = 1 << 30      # pairs per frhip_cross_hist launch: keeps one launch short on a shared device
+
+
+def cross_hist_bands(n, pairs_per_launch=CROSS_HIST_PAIRS_PER_LAUNCH):
+    """row boundaries [0, b1, ..., n] of the bands for cross_hist: each band [i0, i0 + h) holds about h i0 + h^2 / 2 <=
+    pairs_per_launch pairs, h a multiple of the kernel's 128-row tile"""
+    bounds, i0 = [0], 0
+    while i0 < n:
+        h = math.isqrt(i0 * i0 + 2 * pairs_per_launch) - i0
+        rows = max(128, h // 128 * 128)
+        i0 = min(n, i0 + rows)
+        bounds.append(i0)
+    return bounds
+
+
+def cross_hist(e, labels_i64, bounds=None):
+    """every pair j < i of e [n,d] counted without a pair list -> (hist_genuine, hist_imposter) int64 [100001] (the reference's
+    bins) and (thr_genuine, thr_imposter) int64 [100002] (threshold slots, include/frhip.h frhip_cross_hist), on the device.
+    `bounds`: row boundaries of the launches, 0 first and n last (default cross_hist_bands(n))."""
+    n, d = e.shape
+    dev = e.device
+    bounds = cross_hist_bands(n) if bounds is None else list(bounds)
+    if not bounds or bounds[0] != 0 or bounds[-1] != n or any(b1 < b0 for b0, b1 in zip(bounds, bounds[1:])):
+        raise ValueError("cross_hist: bounds %r do not cover [0, %d) in order" % (bounds[:8], n))
+    hg = torch.zeros((100001,), dtype=torch.int64, device=dev)
+    hi = torch.zeros((100001,), dtype=torch.int64, device=dev)
+    tg = torch.zeros((100002,), dtype=torch.int64, device=dev)
+    ti = torch.zeros((100002,), dtype=torch.int64, device=dev)
+    for i0, i1 in zip(bounds, bounds[1:]):
+        check(lib().frhip_cross_hist(_p(e), _p(labels_i64), n, d, i0, i1, _p(hg), _p(hi), _p(tg), _p(ti), _s()), "frhip_cross_hist")
+    return hg, hi, tg, ti
 
 
 # ------------------------------------------------------------------------------------------ fp8 weight path (BASELINE cfg 5)

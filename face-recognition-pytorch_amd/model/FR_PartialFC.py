@@ -216,10 +216,16 @@ class Model(nn.Module):
         name = outputs[0]["dataset_name"]
         labels = np.concatenate([np.asarray(o[f"{name}_label_list"]).reshape(-1) for o in outputs])
         embeds = np.concatenate([np.asarray(o[f"{name}_embedding"]) for o in outputs])
-        hg, hi, scores, pair_labels = ev.cross_score(embeds, labels)
+        # conf.cross_test_streaming (not in the reference): histograms and accuracy from one pass that keeps no pair list, so the
+        # test runs at sizes whose N^2 / 2 scores would not fit in memory; same results as the list route
+        streaming = getattr(self.conf, "cross_test_streaming", False)
+        if streaming:
+            hg, hi = ev.cross_histograms(embeds, labels)
+        else:
+            hg, hi, scores, pair_labels = ev.cross_score(embeds, labels)
         roc, eer_th = ev.performance_roc(hg, hi, min_level=getattr(self.conf, "min_level", 3),
                                          max_level=getattr(self.conf, "max_level", 9))
-        acc = ev.performance_acc(scores, pair_labels, eer_th)
+        acc = ev.cross_accuracy(embeds, labels, eer_th) if streaming else ev.performance_acc(scores, pair_labels, eer_th)
         return {"dataset_name": name, "acc": acc, "roc": roc, "eer_th": eer_th,
                 "infer_time": float(np.mean([o[f"{name}_infer_time"] for o in outputs]))}
 

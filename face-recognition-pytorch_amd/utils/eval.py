@@ -4,6 +4,9 @@ Same functions / return shapes as /root/reference/utils/eval.py: `pair_score(emb
 (hist_genuine[100001], hist_imposter[100001], score_list), `performance_roc(hist_genuine, hist_imposter, min_level,
 max_level)` -> (roc report string, eer_threshold), `performance_acc(score_list, label_list, th)` -> accuracy in %,
 `cross_score(embeddings, labels)` -> (hist_genuine, hist_imposter, score_list, label_list) over all pairs j < i (:102-137).
+`cross_histograms(embeddings, labels)` and `cross_accuracy(embeddings, labels, th)` (not in the reference) give the same
+histograms and the same accuracy as cross_score + performance_acc from one pass over the pairs that keeps no pair list
+(frhip_cross_hist), so the cross test runs at any N.
 pair_score runs on the MI355X (frhip_pair_score: float64 accumulation of float32 differences in the reference's
 order, so `int(99999*score)` is bit-exact); the ROC scan and accuracy are host logic on 100 001-bin histograms
 (the reference runs them on the host too) restated with numpy cumulative sums instead of Python loops.
@@ -72,3 +75,48 @@ def performance_acc(score_list, label_list, th):
     fr = int(np.sum((score_list <= th / 1e5) & (label_list == 1)))
     fa = int(np.sum((score_list > th / 1e5) & (label_list == 0)))
     return (1 - (fa + fr) / (len(score_list))) * 100
+
+
+# one-entry cache of the last cross_hist pass: cross_histograms and cross_accuracy on the same inputs share it
+_CROSS_CACHE = {}
+
+
+def _cross_counts(embeddings, labels):
+    """-> (hist_genuine, hist_imposter, thr_genuine, thr_imposter) int64 numpy, n, from one frhip_cross_hist pass (cached)"""
+    from frhip import ops
+    if not torch.cuda.is_available():
+        raise RuntimeError("utils.eval cross histograms (frhip) need the MI355X; there is no CPU path")
+    e, lab = _dev(embeddings, torch.float32), _dev(labels, torch.int64).view(-1)
+    if e.dim() != 2 or lab.numel() != e.shape[0]:
+        raise ValueError("cross histograms: embeddings [n, d] and n labels expected, got %s and %d" % (tuple(e.shape), lab.numel()))
+    c = _CROSS_CACHE.get("last")
+    if c is not None and c[0].shape == e.shape and torch.equal(c[0], e) and torch.equal(c[1], lab):
+        return c[2], e.shape[0]
+    counts = tuple(h.cpu().numpy() for h in ops.cross_hist(e, lab))
+    own = lambda t, src: t.clone() if torch.is_tensor(src) and t.data_ptr() == src.data_ptr() else t   # noqa: E731
+    _CROSS_CACHE["last"] = (own(e, embeddings), own(lab, labels), counts)
+    return counts, e.shape[0]
+
+
+def cross_histograms(embeddings, labels, metric="euclidean"):
+    """(hist_genuine[100001], hist_imposter[100001]) float64 of every pair j < i: element for element those of cross_score, without
+    the pair list; they go straight into performance_roc"""
+    assert metric in ["euclidean", "cosine"], "Invalid metric !!!"
+    (hg, hi, _, _), _ = _cross_counts(embeddings, labels)
+    return hg.astype(np.float64), hi.astype(np.float64)
+
+
+def cross_accuracy(embeddings, labels, th, metric="euclidean"):
+    """performance_acc(score_list, label_list, th) of cross_score's lists, exactly, from the threshold-slot histograms:
+    fr = genuine pairs with score <= th / 1e5, fa = imposter pairs with score > th / 1e5.  th: an integer in [0, 100000]
+    (performance_roc's eer_threshold is one)."""
+    assert metric in ["euclidean", "cosine"], "Invalid metric !!!"
+    if not (float(th).is_integer() and 0 <= th <= 100000):
+        raise ValueError("cross_accuracy: th = %r is not an integer in [0, 100000]" % (th,))
+    t = int(th)
+    (_, _, tg, ti), n = _cross_counts(embeddings, labels)
+    if n < 2:
+        raise ValueError("cross_accuracy: %d embeddings make no pair" % n)
+    fr = int(tg[:t + 1].sum())
+    fa = int(ti[t + 1:].sum())
+    return (1 - (fa + fr) / (n * (n - 1) // 2)) * 100

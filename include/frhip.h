@@ -430,6 +430,18 @@ int frhip_pair_score(const float* e1, const float* e2, const int64_t* labels, in
  * l = i (i - 1) / 2 + j; scores / pair_labels float64 [n (n - 1) / 2] (pair label 1.0 = same identity), hist_idx int32 */
 int frhip_cross_score(const float* e, const int64_t* labels, int n, int d, double* scores, double* pair_labels,
                       int* hist_idx, int* hist_genuine, int* hist_imposter, frhip_stream_t stream);
+/* utils/eval.py:102-137 cross test without the pair list: the pairs (i, j < i) with i in the band [i0, i1) of e [n][d] ADD into
+ * four uint64 histograms that the caller zeroes once; launches over disjoint bands that cover [0, n) accumulate the whole
+ * triangle, in any order and split, to the same counts.  Same per-pair arithmetic as frhip_cross_score (float64 sum of squared
+ * float32 differences in ascending k, score = 1 - sum / 4).
+ *   hist_genuine / hist_imposter [100001]: the reference's bins int(99999 * score), pairs whose bin lies in [0, 100000] only --
+ *     equal to frhip_cross_score's histograms.
+ *   thr_genuine / thr_imposter [100002]: every pair with a non-NaN score, in slot t = the smallest t in [0, 100001] with
+ *     score <= t / 1e5 (correctly rounded double quotient; <= 0 -> 0, > 1 -> 100001).  For an integer th in [0, 100000]:
+ *     #{genuine: score <= th / 1e5} = sum_{t <= th} thr_genuine[t], #{imposter: score > th / 1e5} = sum_{t > th} thr_imposter[t].
+ * Device memory stays O(n d) at any n.  Bad arguments (n < 0, d <= 0, a band outside [0, n]) return FRHIP_EINVAL. */
+int frhip_cross_hist(const float* e, const int64_t* labels, int64_t n, int d, int64_t i0, int64_t i1, uint64_t* hist_genuine,
+                     uint64_t* hist_imposter, uint64_t* thr_genuine, uint64_t* thr_imposter, frhip_stream_t stream);
 
 /* ---- recompute-style stem (stride 1): conv3x3(3->64) -> BN -> ReLU -> MaxPool(3,2,1) of nets/resnet.py:232-235 without ever
  * writing the conv output map or an im2col matrix; every pass recomputes the conv from x [b,3,h,w] fp32 NCHW and
