@@ -3,19 +3,12 @@
 // Reference semantics: nn.BatchNorm2d / nn.BatchNorm1d defaults (eps 1e-5, momentum 0.1, biased batch variance
 // for normalisation, unbiased for running_var) as used by /root/reference/nets/resnet.py:81-86, :187, :196-199,
 // and the residual add of BasicBlock.forward (:89-103).
-#include <cstdlib>
 #include "common.h"
 #include "frhip.h"
 
 namespace frhip {
 
 constexpr int EW_THREADS = 256;
-#ifndef EW_UNROLL
-#define EW_UNROLL 2
-#endif
-#ifndef EW_ROWS
-#define EW_ROWS 16
-#endif
 constexpr int RED_GROUPS = 16;      // second-level partial count
 
 template <typename T> struct EW {
@@ -228,32 +221,24 @@ __global__ __launch_bounds__(SMALL ? 256 : 1024) void bn_bwd_finalize_kernel(con
 // registers and the row loop is pure streaming.
 // Streaming accesses of the element-wise passes.  Every operand of bn_apply / bn_bwd_apply is read exactly once, and the
 // producer wrote it a whole conv earlier: non-temporal loads (no allocation in L2 / the last-level cache on the way in)
-// are worth 0.45 ms of the 29.5-ms ResNet50 step (tools/nt_ab.sh, two passes: 30.54 / 30.67 -> 30.15 / 30.15 ms on one box,
+// are worth 0.45 ms of the 29.5-ms ResNet50 step (two passes: 30.54 / 30.67 -> 30.15 / 30.15 ms on one box,
 // 29.46 / 29.52 -> 29.06 / 29.10 on another).  A micro-benchmark that re-reads ONE buffer says the opposite for tensors
 // below ~100 MB (they sit in the 256-MB last-level cache between its iterations) -- the step is the judge.  Non-temporal
-// STORES measured neutral to slightly negative in the step (the consumer conv wants those lines).
-// g_ew_nt bits: 1 = non-temporal loads (residual / backward passes), 4 = also in the plain apply, 2 = non-temporal stores;
-// FRHIP_EW_NT_MB = smallest tensor (MB) that gets them.
+// STORES measured neutral to slightly negative in the step (the consumer conv wants those lines), and so did non-temporal loads in
+// the plain apply pass: it is better off with cached loads of the tensor the convolution has just written (26.34 vs 26.40 ms over
+// four same-box A/B rounds, 26.67 vs 26.73 over two more).  So: non-temporal loads in the residual apply and the backward apply,
+// plain loads everywhere else, plain stores everywhere.
 template <typename T, bool NT> __device__ __forceinline__ Vec16<T> ew_load(const T* p) {
     Vec16<T> r;
     if constexpr (NT) r.v = __builtin_nontemporal_load(reinterpret_cast<const decltype(r.v)*>(p));
     else r = *reinterpret_cast<const Vec16<T>*>(p);
     return r;
 }
-template <typename T, bool NT> __device__ __forceinline__ void ew_store(T* p, const Vec16<T>& x) {
-    if constexpr (NT) __builtin_nontemporal_store(x.v, reinterpret_cast<decltype(x.v)*>(p));
-    else *reinterpret_cast<Vec16<T>*>(p) = x;
-}
-static size_t EW_NT_BYTES = (size_t)(getenv("FRHIP_EW_NT_MB") ? atoi(getenv("FRHIP_EW_NT_MB")) : 0) << 20;
-// bit 0: non-temporal loads in the residual / backward-apply passes, bit 2: in the plain BatchNorm-apply pass too, bit 1: non-temporal
-// stores.  Default 1.  (Round 1 had 5; with the round-2 tile choices the plain apply pass is better off with cached loads of the
-// tensor the convolution has just written: 26.34 vs 26.40 ms over four same-box A/B rounds, 26.67 vs 26.73 over two more.)
-static int g_ew_nt = getenv("FRHIP_EW_NT") ? atoi(getenv("FRHIP_EW_NT")) : 1;
 
 // INPLACE: out IS y (frhip_conv_fwd_affine's unfused route normalises the convolution's output where it lies).  Two __restrict__ pointers
 // to one buffer would be undefined behaviour -- the compiler may then move a later row's load across an earlier row's store -- so this
 // instantiation reads through `out` itself.
-template <typename T, bool NTL, bool NTS, bool RS = false, bool INPLACE = false>
+template <typename T, bool NTL, bool RS = false, bool INPLACE = false>
 __global__ __launch_bounds__(EW_THREADS) void bn_apply_kernel(const T* __restrict__ y_in, const float* __restrict__ scale,
                                                               const float* __restrict__ shift, const T* __restrict__ res,
                                                               const float* __restrict__ rscale, const float* __restrict__ rshift,
@@ -269,7 +254,7 @@ __global__ __launch_bounds__(EW_THREADS) void bn_apply_kernel(const T* __restric
         sc[e] = scale[cg * EPV + e]; sh[e] = shift[cg * EPV + e];
         rs[e] = rscale ? rscale[cg * EPV + e] : 1.f; rb[e] = rscale ? rshift[cg * EPV + e] : 0.f;
     }
-#pragma unroll EW_UNROLL
+#pragma unroll 2
     for (int r = blockIdx.x * rlanes + rl; r < rows; r += gridDim.x * rlanes) {
         const size_t idx = (size_t)r * C + cg * EPV;
         Vec16<T> a = ew_load<T, NTL>(y + idx);
@@ -296,12 +281,12 @@ __global__ __launch_bounds__(EW_THREADS) void bn_apply_kernel(const T* __restric
                 a.set(e, relu ? fmaxf(o, 0.f) : o);
             }
         }
-        ew_store<T, NTS>(out + idx, a);
+        *reinterpret_cast<Vec16<T>*>(out + idx) = a;
     }
 }
 
 // dy = ca * d_eff + cb * y + cc,  d_eff = dout * mask
-template <typename T, bool NTL, bool NTS, bool RS = false>
+template <typename T, bool NTL, bool RS = false>
 __global__ __launch_bounds__(EW_THREADS) void bn_bwd_apply_kernel(const T* __restrict__ dout, const T* __restrict__ y,
                                                                   const float* __restrict__ ca, const float* __restrict__ cb,
                                                                   const float* __restrict__ cc, const float* __restrict__ mscale,
@@ -317,7 +302,7 @@ __global__ __launch_bounds__(EW_THREADS) void bn_bwd_apply_kernel(const T* __res
         a_[e] = ca[cg * EPV + e]; b_[e] = cb[cg * EPV + e]; c_[e] = cc[cg * EPV + e];
         ms[e] = mscale ? mscale[cg * EPV + e] : 0.f; mb[e] = mscale ? mshift[cg * EPV + e] : 1.f;
     }
-#pragma unroll EW_UNROLL
+#pragma unroll 2
     for (int r = blockIdx.x * rlanes + rl; r < rows; r += gridDim.x * rlanes) {
         const size_t idx = (size_t)r * C + cg * EPV;
         const Vec16<T> d = ew_load<T, NTL>(dout + idx);
@@ -330,7 +315,7 @@ __global__ __launch_bounds__(EW_THREADS) void bn_bwd_apply_kernel(const T* __res
             const float de = (yy * ms[e] + mb[e] > 0.f) ? d.get(e) * ks : 0.f;
             b.set(e, a_[e] * de + b_[e] * yy + c_[e]);
         }
-        ew_store<T, NTS>(dy + idx, b);
+        *reinterpret_cast<Vec16<T>*>(dy + idx) = b;
     }
 }
 
@@ -391,8 +376,8 @@ static int grid_for(size_t work_items, int per_block) {
 static int ew_row_blocks(int rows, int c, int dtype) {
     const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
     const int rlanes = EW_THREADS / (c / epv);
-    // >= 8 rows per thread so the per-channel vectors (up to 40 floats per thread) are amortised
-    int b = (rows + rlanes * EW_ROWS - 1) / (rlanes * EW_ROWS);
+    // about 16 rows per thread so the per-channel vectors (up to 40 floats per thread) are amortised
+    int b = (rows + rlanes * 16 - 1) / (rlanes * 16);
     if (b > 2048) b = 2048;
     return b < 1 ? 1 : b;
 }
@@ -465,9 +450,8 @@ static const float* fold_partials(const float* partial, int& nparts, int c, floa
     return scratch;
 }
 static int fin_threads(int nparts) { return nparts > 64 ? 1024 : 256; }
-// FRHIP_BN_FIN_SMALL (default 1): folds of more than 64 rows by 256-thread blocks of 16 channels (0: 1024-thread blocks of 64 channels)
-static const int g_fin_small = getenv("FRHIP_BN_FIN_SMALL") ? atoi(getenv("FRHIP_BN_FIN_SMALL")) : 1;
-static bool fin_small(int nparts) { return g_fin_small == 1 ? nparts > 64 : (g_fin_small >= 2 ? nparts >= g_fin_small : false); }   // >= 2: a row threshold
+// folds of more than 64 rows by 256-thread blocks of 16 channels (rather than 1024-thread blocks of 64 channels)
+static bool fin_small(int nparts) { return nparts > 64; }
 
 extern "C" int frhip_bn_finalize(const float* partial, int nparts, float* scratch, int c, float count,
                                  const float* gamma, const float* beta, float* running_mean, float* running_var,
@@ -531,10 +515,10 @@ extern "C" int frhip_bn_apply_rs(int dtype, const void* y, const float* scale, c
     if (!rowscale || rows_per <= 0) { set_error("frhip_bn_apply_rs: rowscale and rows_per are required"); return FRHIP_EINVAL; }
     const int blocks = ew_row_blocks(rows, c, dtype);
     if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL((bn_apply_kernel<bf16_t, false, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)y, scale,
+        hipLaunchKernelGGL((bn_apply_kernel<bf16_t, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)y, scale,
                            shift, (const bf16_t*)res, nullptr, nullptr, 0, (bf16_t*)out, rows, c, rowscale, rows_per);
     else
-        hipLaunchKernelGGL((bn_apply_kernel<float, false, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const float*)y, scale,
+        hipLaunchKernelGGL((bn_apply_kernel<float, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const float*)y, scale,
                            shift, (const float*)res, nullptr, nullptr, 0, (float*)out, rows, c, rowscale, rows_per);
     return check_launch("frhip_bn_apply_rs");
 }
@@ -559,10 +543,10 @@ extern "C" int frhip_bn_bwd_apply_rs(int dtype, const void* dout, const void* y,
     if (!rowscale || rows_per <= 0) { set_error("frhip_bn_bwd_apply_rs: rowscale and rows_per are required"); return FRHIP_EINVAL; }
     const int blocks = ew_row_blocks(rows, c, dtype);
     if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, false, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)dout,
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)dout,
                            (const bf16_t*)y, ca, cb, cc, nullptr, nullptr, (bf16_t*)dy, rows, c, rowscale, rows_per);
     else
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const float*)dout,
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const float*)dout,
                            (const float*)y, ca, cb, cc, nullptr, nullptr, (float*)dy, rows, c, rowscale, rows_per);
     return check_launch("frhip_bn_bwd_apply_rs");
 }
@@ -572,20 +556,17 @@ extern "C" int frhip_bn_apply(int dtype, const void* y, const float* scale, cons
                               hipStream_t stream) {
     if (!shape_ok(dtype, c, "frhip_bn_apply")) return FRHIP_EINVAL;
     const int blocks = ew_row_blocks(rows, c, dtype);
-    const size_t bytes = (size_t)rows * c * (dtype == FRHIP_DT_BF16 ? 2 : 4);
-    const bool ntl = (g_ew_nt & 1) && bytes >= EW_NT_BYTES && (res != nullptr || (g_ew_nt & 4)), nts = (g_ew_nt & 2) && bytes >= EW_NT_BYTES / 2;
-#define BN_APPLY_GO(T, L, S)                                                                                                  \
-    hipLaunchKernelGGL((bn_apply_kernel<T, L, S>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const T*)y, scale, shift,     \
+#define BN_APPLY_GO(T, L)                                                                                                     \
+    hipLaunchKernelGGL((bn_apply_kernel<T, L>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const T*)y, scale, shift,        \
                        (const T*)res, res_scale, res_shift, relu, (T*)out, rows, c)
 #define BN_APPLY_PICK(T)                                                                                                      \
-    do { if (ntl && nts) BN_APPLY_GO(T, true, true); else if (ntl) BN_APPLY_GO(T, true, false);                               \
-         else if (nts) BN_APPLY_GO(T, false, true); else BN_APPLY_GO(T, false, false); } while (0)
+    do { if (res) BN_APPLY_GO(T, true); else BN_APPLY_GO(T, false); } while (0)      // non-temporal loads in the residual pass
     if (y == out) {            // in place: the instantiation that reads through `out` (plain loads and stores)
         if (dtype == FRHIP_DT_BF16)
-            hipLaunchKernelGGL((bn_apply_kernel<bf16_t, false, false, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, nullptr, scale, shift,
+            hipLaunchKernelGGL((bn_apply_kernel<bf16_t, false, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, nullptr, scale, shift,
                                (const bf16_t*)res, res_scale, res_shift, relu, (bf16_t*)out, rows, c);
         else
-            hipLaunchKernelGGL((bn_apply_kernel<float, false, false, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, nullptr, scale, shift,
+            hipLaunchKernelGGL((bn_apply_kernel<float, false, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, nullptr, scale, shift,
                                (const float*)res, res_scale, res_shift, relu, (float*)out, rows, c);
         return check_launch("frhip_bn_apply");
     }
@@ -600,17 +581,12 @@ extern "C" int frhip_bn_bwd_apply(int dtype, const void* dout, const void* y, co
                                   int rows, int c, hipStream_t stream) {
     if (!shape_ok(dtype, c, "frhip_bn_bwd_apply")) return FRHIP_EINVAL;
     const int blocks = ew_row_blocks(rows, c, dtype);
-    const size_t bytes = (size_t)rows * c * (dtype == FRHIP_DT_BF16 ? 2 : 4);
-    const bool ntl = (g_ew_nt & 1) && bytes >= EW_NT_BYTES, nts = (g_ew_nt & 2) && bytes >= EW_NT_BYTES / 2;
-#define BN_BWD_GO(T, L, S)                                                                                                    \
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, L, S>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const T*)dout, (const T*)y, \
-                       ca, cb, cc, mask_scale, mask_shift, (T*)dy, rows, c)
-#define BN_BWD_PICK(T)                                                                                                        \
-    do { if (ntl && nts) BN_BWD_GO(T, true, true); else if (ntl) BN_BWD_GO(T, true, false);                                   \
-         else if (nts) BN_BWD_GO(T, false, true); else BN_BWD_GO(T, false, false); } while (0)
-    if (dtype == FRHIP_DT_BF16) BN_BWD_PICK(bf16_t); else BN_BWD_PICK(float);
-#undef BN_BWD_PICK
-#undef BN_BWD_GO
+    if (dtype == FRHIP_DT_BF16)
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)dout,
+                           (const bf16_t*)y, ca, cb, cc, mask_scale, mask_shift, (bf16_t*)dy, rows, c);
+    else
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const float*)dout,
+                           (const float*)y, ca, cb, cc, mask_scale, mask_shift, (float*)dy, rows, c);
     return check_launch("frhip_bn_bwd_apply");
 }
 

@@ -26,6 +26,11 @@ namespace frhip {
 
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+// Raises a kernel's dynamic-LDS limit to `bytes` on the current device, once per (kernel, device); on failure sets the error
+// "<who>: cannot raise dynamic LDS to <bytes> bytes" and returns FRHIP_ELAUNCH.  Safe to call from concurrent host threads.
+int set_dynamic_lds(const void* fn, int bytes, const char* who);
+// Compute units of the current device, cached per device (256 when the runtime cannot say).
+int device_cu_count();
 
 // ---- buffer resource (raw, stride 0).  OOB reads return 0 -- used for conv zero padding.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, uint32_t bytes) {
@@ -51,18 +56,9 @@ __device__ __forceinline__ u32x4_t make_rsrc_words(const void* p, uint32_t bytes
     const uint64_t a = (uint64_t)(uintptr_t)p;
     return u32x4_t{(uint32_t)a, (uint32_t)(a >> 32) & 0xffffu, bytes, 0x00020000u};
 }
-#ifndef FRHIP_DMA_ASM
-#define FRHIP_DMA_ASM 1      // 0: A/B build -- the same call sites through the builtin (and the compiler's waits)
-#endif
 __device__ __forceinline__ void glds16_asm(u32x4_t rsrc, uint32_t lds_addr, uint32_t voff) {
-#if FRHIP_DMA_ASM
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
                  :: "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc) : "memory");
-#else
-    const void* p = reinterpret_cast<const void*>((uintptr_t)rsrc[0] | ((uintptr_t)rsrc[1] << 32));
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, rsrc[2], 0x00020000),
-                                             (__attribute__((address_space(3))) void*)(uintptr_t)__builtin_amdgcn_readfirstlane(lds_addr), 16, voff, 0, 0, 0);
-#endif
 }
 
 // ---- element <-> float
@@ -173,16 +169,13 @@ __device__ __forceinline__ void gelu_parts(float h, float& cdf, float& pdf) {
 // instructions (32 issue cycles per element) against 12 + 2 (64) of the A&S 7.1.26 form, which the fp32 validation mode keeps.
 // The Swin MLP epilogues are bound by exactly this arithmetic (a 256 x 256 x 256 tile: 3.4 us of MFMA, 9 us of exact GELU).
 // gelu'(h) is the derivative of the SAME approximation (one shared exponential, no second transcendental).
-#ifndef FRHIP_GELU_EXACT
-#define FRHIP_GELU_EXACT 0            // A/B switch: 1 = the exact erf form in bf16 mode too
-#endif
 constexpr float GELU_C1 = 0.7999131f, GELU_C3 = 0.03497319f, GELU_L2E2 = 2.f * 1.4426950408889634f;
 __device__ __forceinline__ float gelu_fast_sigma(float h, float h2) {
     const float w = h * __builtin_fmaf(h2, GELU_C3 * GELU_L2E2, GELU_C1 * GELU_L2E2);      // 2u log2(e)
     return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-w));
 }
 template <typename T> __device__ __forceinline__ float gelu_value(float h) {
-    if constexpr (sizeof(T) == 2 && !FRHIP_GELU_EXACT) {
+    if constexpr (sizeof(T) == 2) {
         return h * gelu_fast_sigma(h, h * h);
     } else {
         float cdf, pdf;
@@ -191,7 +184,7 @@ template <typename T> __device__ __forceinline__ float gelu_value(float h) {
     }
 }
 template <typename T> __device__ __forceinline__ float gelu_slope(float h) {
-    if constexpr (sizeof(T) == 2 && !FRHIP_GELU_EXACT) {
+    if constexpr (sizeof(T) == 2) {
         const float h2 = h * h, r = gelu_fast_sigma(h, h2);
         const float q = __builtin_fmaf(h2, 6.f * GELU_C3, 2.f * GELU_C1);                   // d(2u)/dh
         return __builtin_fmaf(h * __builtin_fmaf(-r, r, r), q, r);                          // r + h r (1 - r) q

@@ -330,14 +330,7 @@ static int head_launch_mk(const NtGeom& g, const void* ehat, const void* what, c
     const int lds = Tile::template lds_bytes<T>();
     const MarginArg<MK, FILT> mc = mcx;           // plain ArcFace: the MarginConst part only
     auto kern = head_kernel<T, FWD, MK, FILT>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            set_error("head: cannot raise dynamic LDS to %d bytes", lds);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "head")) return FRHIP_ELAUNCH;
     hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(256), lds, stream, g, ehat, what, labels, mc, pmax, psum,
                        zt, rmax, rsum, gscale, upstream, dt, ldt, dtt, ldtt, mtiles, ntiles);
     return check_launch("head");

@@ -12,7 +12,7 @@
 #include "frhip.h"
 
 namespace frhip {
-extern int g_epi_lean;      // igemm_halo.hip: frhip_set_epi_lean / FRHIP_EPI_LEAN
+extern int g_epi_lean;      // igemm_halo.hip: frhip_set_epi_lean
 
 constexpr float FP8_MAX = 448.f;
 
@@ -187,14 +187,7 @@ static int nt8_launch(const NtGeom& g, const void* a, const void* b, const float
     const int mtiles = (g.M + Tile::BM - 1) / Tile::BM, ntiles = (g.Nout + Tile::BN - 1) / Tile::BN;
     const int lds = Tile::template lds_bytes<bf16_t>();
     auto kern = nt8_kernel<WM, WN, MT, LEAN>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            set_error("igemm_fp8: cannot raise dynamic LDS to %d bytes", lds);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "igemm_fp8")) return FRHIP_ELAUNCH;
     hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(Tile::THREADS), lds, stream, g, a, b, wscale, ascale, out, stats, br, mtiles, ntiles);
     return check_launch("igemm_fp8");
 }
@@ -261,14 +254,7 @@ static int halo8_run(const void* x8, const void* w8, const float* wscale, float 
     static const EpiBnRed none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, {0, 0, 0, 0, 0, 0}, nullptr, nullptr, 0};
     const bool lean = g_epi_lean && epi_lean_ok(true, g.M, k, Tile::BM, Tile::BN, none);
     auto kern = lean ? halo8_kernel<4, 1, 4, 1, true> : halo8_kernel<4, 1, 4, 1, false>;
-    static bool attr_done[2] = {false, false};
-    if (!attr_done[lean]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            set_error("igemm_fp8(halo): cannot raise dynamic LDS to %d bytes", lds);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done[lean] = true;
-    }
+    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "igemm_fp8(halo)")) return FRHIP_ELAUNCH;
     hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(Tile::THREADS), lds, stream, g, x8, w8, wscale, ascale, y, stats, none, mtiles, ntiles);
     return check_launch("igemm_fp8(halo)");
 }

@@ -13,9 +13,6 @@
 // `s_waitcnt vmcnt(PIECES)` + one raw s_barrier per iteration retires exactly the previous iteration's loads and
 // leaves the current iteration's in flight across the barrier.
 #pragma once
-#ifndef HALO_A_AUX
-#define HALO_A_AUX 0      // cache policy of the activation-window loads (experiment switch)
-#endif
 #include <type_traits>
 #include "igemm_nt.h"
 
@@ -96,7 +93,7 @@ struct HaloMainloop {
             // rows outside the tensor need no test: p < 0 wraps to an offset beyond 2 GiB, p >= M lies beyond a_bytes -- the buffer
             // range check zero-fills both (a_bytes = M * C * sizeof(T) < 2^31)
             const uint32_t off = row0_off + (uint32_t)(piece * 8 * g.C + c0) * (uint32_t)sizeof(T);
-            glds16<HALO_A_AUX>(ra, smem + hb * Tile::HALO_BYTES + piece * 1024, off);
+            glds16(ra, smem + hb * Tile::HALO_BYTES + piece * 1024, off);
         };
         // XF: BatchNorm + ReLU of the pieces THIS wave loaded (after its own vmcnt(0), before the barrier that publishes them).
         // Rows outside the tensor were zero-filled by the DMA and stay zero: the convolution pads the ACTIVATED tensor.

@@ -1,6 +1,5 @@
 // Launcher of the halo-tile 3x3/s1/p1 convolution (see igemm_halo.h).  Reached through frhip_conv_fwd /
 // frhip_conv_dgrad when the geometry matches; the generic NT kernel covers everything else.
-#include <cstdlib>
 #include "igemm_halo.h"
 #include "igemm_halo_wide.h"
 #include "frhip.h"
@@ -115,8 +114,8 @@ __global__ __launch_bounds__(256, 2) void halo_wide_kernel(HaloGeom g, const voi
     }
 }
 
-// FRHIP_EPI_LEAN=0: always the general store epilogue (A/B switch; the lean kernels are bit-identical)
-int g_epi_lean = getenv("FRHIP_EPI_LEAN") ? atoi(getenv("FRHIP_EPI_LEAN")) : 1;
+// frhip_set_epi_lean(0): always the general store epilogue (the lean kernels are bit-identical)
+int g_epi_lean = 1;
 
 static int halo_wide_launch(const HaloGeom& g, const void* a, const void* b, void* out, const void* res, float* stats,
                             const EpiBnRed& br, hipStream_t stream) {
@@ -124,14 +123,7 @@ static int halo_wide_launch(const HaloGeom& g, const void* a, const void* b, voi
     const int mtiles = (g.M + Tile::BM - 1) / Tile::BM, ntiles = (g.Nout + Tile::BN - 1) / Tile::BN;
     const bool lean = g_epi_lean && epi_lean_ok(true, g.M, g.Nout, Tile::BM, Tile::BN, br);
     auto kern = lean ? halo_wide_kernel<true> : halo_wide_kernel<false>;
-    static bool attr_done[2] = {false, false};
-    if (!attr_done[lean]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Tile::LDS) != hipSuccess) {
-            set_error("igemm_halo: cannot raise dynamic LDS to %d bytes", Tile::LDS);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done[lean] = true;
-    }
+    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), Tile::LDS, "igemm_halo")) return FRHIP_ELAUNCH;
     hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(Tile::THREADS), Tile::LDS, stream, g, a, b, out, res, stats, br, mtiles, ntiles);
     return check_launch("igemm_halo_wide");
 }
@@ -148,19 +140,12 @@ static int halo_launch(const HaloGeom& g, const void* a, const void* b, void* ou
     if constexpr (HAS_LEAN) lean = g_epi_lean && epi_lean_ok(true, g.M, g.Nout, Tile::BM, Tile::BN, br);
     auto kern = halo_kernel<T, WM, WN, MT, HBUFS, XF, false>;
     if constexpr (HAS_LEAN) { if (lean) kern = halo_kernel<T, WM, WN, MT, HBUFS, XF, true>; }
-    static bool attr_done[2] = {false, false};
-    if (!attr_done[lean]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            set_error("igemm_halo: cannot raise dynamic LDS to %d bytes", lds);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done[lean] = true;
-    }
+    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "igemm_halo")) return FRHIP_ELAUNCH;
     hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(Tile::THREADS), lds, stream, g, a, b, out, res, stats, br, mtiles, ntiles);
     return check_launch("igemm_halo");
 }
 
-static int g_halo_enabled = getenv("FRHIP_HALO_MODE") ? atoi(getenv("FRHIP_HALO_MODE")) & 3 : 1;     // 2 / 3: force the 4-wave / 8-wave tile
+static int g_halo_enabled = 1;     // frhip_set_conv_halo: 0 off, 1 auto, 2 / 3 force the 4-wave / 8-wave tile
 
 bool halo_applicable(int dtype, int h, int w, int c, int k, int r, int s, int stride, int pad) {
     const int bke = NT_ROWB / (dtype == FRHIP_DT_BF16 ? 2 : 4);
@@ -177,7 +162,7 @@ bool halo_applicable(int dtype, int h, int w, int c, int k, int r, int s, int st
 //       26.33, nowhere 27.0 -- the wide tile earns its keep beside the weight-gradient workgroups of the backward pass; the forward
 //       launches, alone on the chip, are better off with twice as many 64-wide tiles.
 // Every configuration has 256-row tiles: one BN-partial row per 256 output pixels.
-static int g_halo_wide_dirs = getenv("FRHIP_HALO_WIDE_DIRS") ? atoi(getenv("FRHIP_HALO_WIDE_DIRS")) & 3 : 2;
+static int g_halo_wide_dirs = 2;
 static int halo_config(int dtype, int c, int k);
 static int halo_config_w(int dtype, int w, int c, int k, int sign) {
     if ((g_halo_wide_dirs & (sign > 0 ? 1 : 2)) && dtype == FRHIP_DT_BF16 && w <= HaloWideTile::MAXW &&

@@ -393,13 +393,9 @@ inline bool epi_lean_ok(bool bf16, long long M, int Nout, int bm, int bn, const 
 // Output rows of the store epilogue go out with non-temporal stores: a conv / linear output is written once and read one
 // kernel later by a streaming pass (which reads it non-temporally as well), so it should not push the weights and the next
 // operand out of L2 on its way.  Step-level A/B (tools/ab_libs.sh, three passes on one box): ResNet50 28.06 / 27.90 / 28.07 ->
-// 27.83 / 27.85 / 27.87 ms, Swin34 19.31 -> 19.0 ms.  -DEPI_NT_STORE=0 builds the plain-store variant.
-#ifndef EPI_NT_STORE
-#define EPI_NT_STORE 1
-#endif
+// 27.83 / 27.85 / 27.87 ms, Swin34 19.31 -> 19.0 ms.  The plain-store variant was measured and removed.
 template <typename T> __device__ __forceinline__ void epi_store_row(T* p, const Vec16<T>& v) {
-    if constexpr (EPI_NT_STORE) __builtin_nontemporal_store(v.v, reinterpret_cast<decltype(v.v)*>(p));
-    else *reinterpret_cast<Vec16<T>*>(p) = v;
+    __builtin_nontemporal_store(v.v, reinterpret_cast<decltype(v.v)*>(p));
 }
 
 // ---- per-channel sums over a wave's staged tile on the MATRIX pipe (LEAN kernels, bf16).
@@ -487,7 +483,7 @@ __device__ __forceinline__ void nt_epilogue_store_fast(const char* mine, int P, 
     const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, (uint32_t)M * (uint32_t)Nout * (uint32_t)sizeof(T));
     const char* src = mine + rsub * P + chunk * 16;
     auto put = [&](int it, const Vec16<T>& v) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v.v), ro, ops.voff, it * ops.vstep, EPI_NT_STORE ? 2 : 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v.v), ro, ops.voff, it * ops.vstep, 2 /* nt */);
     };
     if (stats && br.y) {
         // BatchNorm-backward partials { sum d, sum d * (y - mean) * invstd }, d = the stored gradient behind the ReLU mask, on the
@@ -654,7 +650,7 @@ __device__ __forceinline__ void nt_epilogue_store_lean(const char* mine, int P, 
                     v.set(e, v.get(e) * gelu_slope<T>(yv[j].get(e)));
                 }
             }
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v.v), ro, voff, it * vstep, EPI_NT_STORE ? 2 : 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v.v), ro, voff, it * vstep, 2 /* nt */);
             if (has_act) {
                 Vec16<T> ga;
 #pragma unroll

@@ -15,7 +15,7 @@ int halo_run(int dtype, const void* a, const void* b, void* out, const void* res
              const float* xf_shift = nullptr, void* xf_out = nullptr);
 
 enum { EPI_STORE = 0, EPI_ATOMIC = 1, EPI_SLAB = 2, EPI_LEAN = 3 };    // SLAB: K split y stores its fp32 partial tile to slab y of `out`; LEAN: nt_epilogue_store_lean
-extern int g_epi_lean;      // igemm_halo.hip: frhip_set_epi_lean / FRHIP_EPI_LEAN
+extern int g_epi_lean;      // igemm_halo.hip: frhip_set_epi_lean
 
 // one output tile (logical id t of `total`)
 template <typename T, int WM, int WN, int MT, int EPI>
@@ -102,20 +102,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 4) void nt_kernel(NtGeom 
     }
 }
 
-// FRHIP_NT_PERSIST=0: one workgroup per tile also for the lean launches (A/B switch)
-static const int g_nt_persist = getenv("FRHIP_NT_PERSIST") ? atoi(getenv("FRHIP_NT_PERSIST")) : 1;
-static int nt_cus() {
-    static int cus[16] = {0};                      // per device: a process that drives a second GPU sizes its grids for THAT chip
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return 256; }
-    if (!cus[dev]) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cus[dev] = v;
-    }
-    return cus[dev];
-}
-
 template <typename T, int WM, int WN, int MT, int EPI>
 static int nt_launch_cfg(const NtGeom& g, const void* a, const void* b, void* out, const void* res,
                          float* stats, const EpiBnRed& br, int splits, hipStream_t stream) {
@@ -123,20 +109,11 @@ static int nt_launch_cfg(const NtGeom& g, const void* a, const void* b, void* ou
     const int mtiles = (g.M + Tile::BM - 1) / Tile::BM, ntiles = (g.Nout + Tile::BN - 1) / Tile::BN;
     const int lds = (EPI == EPI_STORE || EPI == EPI_LEAN) ? Tile::template lds_bytes<T>() : Tile::template lds_bytes<float>();     // ATOMIC / SLAB stage fp32
     auto kern = nt_kernel<T, WM, WN, MT, EPI>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            set_error("igemm_nt: cannot raise dynamic LDS to %d bytes", lds);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "igemm_nt")) return FRHIP_ELAUNCH;
     dim3 grid(mtiles * ntiles, splits);
-    if (EPI == EPI_LEAN && g_nt_persist) {
-        // a multiple of 8: a workgroup's tiles stay on its XCD's share of the remap.  FRHIP_NT_PERSIST_WGS < CU count leaves CUs to the
-        // other stream for the length of the launch (the 8-wave workgroups take the whole register file of the CU they sit on)
-        static const int env_wgs = getenv("FRHIP_NT_PERSIST_WGS") ? atoi(getenv("FRHIP_NT_PERSIST_WGS")) : 0;
-        const unsigned wgs = (unsigned)(env_wgs > 0 ? env_wgs : nt_cus()) & ~7u;
+    if (EPI == EPI_LEAN) {
+        // one workgroup per CU, a multiple of 8: a workgroup's tiles stay on its XCD's share of the remap
+        const unsigned wgs = (unsigned)device_cu_count() & ~7u;
         if (wgs >= 8 && grid.x > wgs) grid.x = wgs;
     }
     hipLaunchKernelGGL(kern, grid, dim3(Tile::THREADS), lds, stream, g, a, b, out, res, stats, br, mtiles, ntiles);

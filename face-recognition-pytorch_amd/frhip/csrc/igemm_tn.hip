@@ -9,17 +9,8 @@
 // of the caller's workspace and one reduce pass adds the slabs in split order (run-to-run identical); a single split
 // adds its tiles into the output directly, in whole 256-byte rows staged through LDS.
 // Reference counterpart: autograd of nn.Conv2d / F.linear (cuDNN wgrad), nets/resnet.py:23-46, nets/PartialFC.py:201.
-#include <cstdlib>
 #include "common.h"
 #include "frhip.h"
-
-// TN_SLAB_NT (build-time experiment switch): bit 0 non-temporal slab stores in the nine-tap kernel, bit 1 non-temporal slab loads
-#ifndef TN_SLAB_NT
-#define TN_SLAB_NT 0
-#endif
-#ifndef T9_AUX
-#define T9_AUX 0          // cache policy of the nine-tap kernel's operand loads (experiment switch)
-#endif
 
 namespace frhip {
 
@@ -272,24 +263,14 @@ __global__ __launch_bounds__(TN_THREADS, 2) void tn_kernel(TnGeom g, const void*
 // the nine taps read the same rows at offsets dy*W + dx): 150-240 MAC/B, and the dy fragments are transposed-read once
 // and reused by all taps.  Padding is resolved at the transposed read (lanes whose row is padding point at a zero
 // block).  Every LDS address is computed once before the K loop.
-//   <2,4,4,1>: 128 co x 64 ci, eight waves, wave tile 64 x 16, 144 accumulator registers
+//   <1,4,4,1>: 64 co x 64 ci, four waves, wave tile 64 x 16, 144 accumulator registers
 //              (a 64 x 32 wave tile needs 288 accumulators: more than the 256 AGPRs, the compiler then shuffles them)
-//   <1,4,4,1>:  64 co x 64 ci, four waves, same wave tile, two workgroups per CU
 // The inner loop is VALU-issue-bound before it is MFMA-bound (an MFMA shadows only ~3 VALU issues), so per fragment
 // read it does ONE select: offsets are stage-relative registers, the stage base is an instruction immediate.
 // Timing-only ablation switches (tools/ablate.py; results are WRONG with any bit set): 1 no per-step barrier, 2 no MFMA,
 // 4 no LDS fragment reads, 8 no in-loop DMA, 16 no epilogue.
 #ifndef FRHIP_ABL
 #define FRHIP_ABL 0
-#endif
-#ifndef T9_DEPTH
-#define T9_DEPTH 6        // window-fragment look-ahead (tools/ablate.py ABL_DEFS sweep, round 2: 4 -> 6 with the stagger below: -3.5 %)
-#endif
-#ifndef T9_PIN
-#define T9_PIN 0
-#endif
-#ifndef T9_STAGGER
-#define T9_STAGGER 8      // experiment: waves 4-7 of the 8-wave tile start every K step T9_STAGGER x 64 clocks late (MI355X_MICROARCH "two waves per SIMD", item 9)
 #endif
 constexpr int T9_MAXW = 56;
 constexpr int T9_QROWS = 192;                               // 24 pieces of 8 rows >= 64 + 2*56 + 2
@@ -469,12 +450,6 @@ void tn_taps9_kernel(TnGeom g, const void* __restrict__ p_ptr, const void* __res
 
     auto compute = [&](auto buf_c) {
         typedef std::integral_constant<int, decltype(buf_c)::value * Cfg::STAGE> Off;
-        if constexpr (T9_STAGGER > 0 && Cfg::NW == 8) {
-            if (wave >= 4) {
-#pragma unroll
-                for (int z = 0; z < T9_STAGGER; ++z) __builtin_amdgcn_s_sleep(1);
-            }
-        }
         // rows past M need no mask: their dy rows were zero-filled and every window row read is finite data or zero
         bool up[4], dn[4], lf[4], rt[4];
         if constexpr (TAB) {
@@ -518,7 +493,7 @@ void tn_taps9_kernel(TnGeom g, const void* __restrict__ p_ptr, const void* __res
         };
         // ring of DEPTH window-fragment sets: group n + DEPTH - 1 is read while group n multiplies (a group is only
         // COF*CIF MFMAs = 64 matrix-pipe cycles, LDS latency under load is several times that)
-        constexpr int DEPTH = T9_DEPTH;
+        constexpr int DEPTH = 6;         // tools/ablate.py ABL_DEFS sweep, round 2: 4 -> 6: -3.5 %
         bf16x8_t qr[DEPTH][CIF];
         loadp(0);
 #pragma unroll
@@ -528,20 +503,6 @@ void tn_taps9_kernel(TnGeom g, const void* __restrict__ p_ptr, const void* __res
             if (n + DEPTH - 1 < 18) loadq(n + DEPTH - 1, qr[(n + DEPTH - 1) % DEPTH]);
             if (n == 3) loadp(1);
             mma(n, qr[n % DEPTH]);
-#if T9_PIN == 1
-            // issue-slot packing: the address selects and the transposed reads of the look-ahead group go BETWEEN this
-            // group's MFMAs (an MFMA keeps the matrix pipe busy for 16 cycles; what is issued in its shadow is free)
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#elif T9_PIN == 2
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-#endif
         }
         if constexpr (TAB) {
             // the next K step's masks: scalar loads, issued behind this step's last fragment reads and consumed after the barrier
@@ -631,8 +592,7 @@ void tn_taps9_kernel(TnGeom g, const void* __restrict__ p_ptr, const void* __res
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { const int k = 4 * j + r; v[r] = acc[k % 9][a][b][k / 9]; }
                     float* p = dst + (((size_t)q * 9 + j) * g.C + ci) * 4;
-                    if constexpr (TN_SLAB_NT & 1) __builtin_nontemporal_store(v, reinterpret_cast<f32x4_t*>(p));
-                    else *reinterpret_cast<f32x4_t*>(p) = v;
+                    *reinterpret_cast<f32x4_t*>(p) = v;
                 }
             }
         }
@@ -672,16 +632,12 @@ void tn_taps9_kernel(TnGeom g, const void* __restrict__ p_ptr, const void* __res
 // with the next image's rows as soon as every wave has consumed it (one barrier per two rows), which leaves a load ten row steps
 // (~2 900 cycles) to land.  16-byte chunks are XOR-swizzled by bit 1 of the pixel slot (x 4) on the source
 // side: the 4 pixel x 64 byte footprint of one LDS cycle of a transposed read then covers all 64 banks once.
-#ifndef R14_PIN
-#define R14_PIN 0         // 1: one transposed read pinned behind each MFMA (left alone the compiler issues them in bursts in front of a fence): 103 -> 96 us
-                          // stand-alone, but +0.1 ms on the step -- the steadier stream takes more from the co-resident main-stream workgroup
-#endif
 struct R14 {
     static constexpr int SLOT = 8192, QOFF = 4096, NSLOT = 7, LDS = NSLOT * SLOT + 128, ROWB = 2048;
 };
 // slabs of the previous launch of a chain (count = 0: none): `count` slabs `step` floats apart, writer's layout, to be ADDED to dw[kc4 * 4][9][C]
 struct R14Prev { const float* slabs; float* dw; int count; size_t step; int kc4, C; };
-__device__ __forceinline__ f32x4_t slab_load(const float* p);
+__device__ __forceinline__ f32x4_t slab_load(const float* p) { return *reinterpret_cast<const f32x4_t*>(p); }
 __device__ __forceinline__ int r14_swz(int p) { return ((p >> 1) & 1) << 2; }
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
@@ -822,11 +778,6 @@ void tn_rows14_kernel(TnGeom g, const void* __restrict__ p_ptr, const void* __re
                 else acc[(dy + 1) * 3 + d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[H & 1], rf[(H + dy + PH) & 3][d], acc[(dy + 1) * 3 + d], 0, 0, 0);
             }
         }
-#if R14_PIN == 1
-        // one transposed read behind each of the first eight MFMAs
-#pragma unroll
-        for (int z = 0; z < 8; ++z) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
-#endif
     };
     auto fence = [&](auto n_c) {                // all but the n newest loads of this wave have landed; then everyone's
         // lgkmcnt(0): this wave's reads of the slot refilled behind the barrier have returned, not merely been issued
@@ -899,24 +850,20 @@ static int g_tn_taps9 = 1;
 //     at most ONE of its workgroups fits a CU, and beside it fit one 73-KB forward / data-gradient workgroup (4 waves) or the
 //     BatchNorm passes' waves: the weight gradient then runs in the shadow of whatever the main stream is doing.
 // Measured on the ResNet50 step (B = 512, two A/B rounds on one box): 29.0 ms (8-wave) -> 28.5 (4-wave) -> 28.2 ms (4-wave, one
-// per CU); the gain from having a side stream at all grows from 0.9 to 1.7 ms.  FRHIP_T9_NARROW=0 / FRHIP_T9_LDS_PAD=0 restore
-// the stand-alone-fastest choice (kernel micro-benchmarks use it).
-static int g_t9_narrow = getenv("FRHIP_T9_NARROW") ? atoi(getenv("FRHIP_T9_NARROW")) : 1;
-static int g_t9_stages4 = getenv("FRHIP_T9_STAGES4") ? atoi(getenv("FRHIP_T9_STAGES4")) : 1;     // A/B switch of the four-stage variant
-static int g_t9_lds_pad = getenv("FRHIP_T9_LDS_PAD") ? atoi(getenv("FRHIP_T9_LDS_PAD")) : 83968;
+// per CU); the gain from having a side stream at all grows from 0.9 to 1.7 ms.  The 8-wave tile was measured and removed.
+// T9_LDS: the dynamic-LDS request of the nine-tap and rows kernels, which makes one workgroup per CU.
+constexpr int T9_LDS = 83968;
 // ---- lane-mask table of the TAB instantiations.  Lane l addresses the pixel rows prow_i(l) = (i >> 1) * 32 + 8 (l >> 4) + ((l & 15) >> 2)
 // + 4 (i & 1) of a K step; K step t covers pixels 64 t .., and a pixel's padding predicates depend on its position inside its image
 // only, so the masks repeat with period H W / gcd(H W, 64) K steps (49 for 7, 14, 28 and 56-wide square maps).  One table per geometry,
 // in module memory, filled on first use (blocking copy: never inside a stream capture -- a warm-up step comes first).
 constexpr int T9_TAB_GEOMS = 8, T9_TAB_MAXP = 64;
 __device__ unsigned long long g_t9_masks[T9_TAB_GEOMS][T9_TAB_MAXP * 16];
-static int g_t9_tab = getenv("FRHIP_T9_MASK_TABLE") ? atoi(getenv("FRHIP_T9_MASK_TABLE")) : 1;
 static bool t9_mask_table(TnGeom& g, hipStream_t stream) {
     // keyed by DEVICE too: g_t9_masks is module memory, every device has its own copy at its own address
     static struct { int device, h, w, period; const unsigned long long* dev; } cache[T9_TAB_GEOMS];
     static int used = 0;
     g.mask_tab = nullptr; g.mask_period = 0;
-    if (!g_t9_tab) return false;
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) { (void)hipGetLastError(); return false; }
     for (int i = 0; i < used; ++i)
@@ -958,73 +905,37 @@ static bool t9_mask_table(TnGeom& g, hipStream_t stream) {
 template <int WCO, int WCI, int COF, int CIF, bool XF = false, int NST = 2, int QROWS = T9_QROWS, bool TAB = false>
 static int tn_taps9_launch(const TnGeom& g, const void* p, const void* q, float* out, int splits, hipStream_t stream) {
     typedef T9Cfg<WCO, WCI, COF, CIF, NST, QROWS> Cfg;
+    static_assert(Cfg::LDS <= T9_LDS, "stages and epilogue fit the LDS request");
     const int co_tiles = (g.Kc + Cfg::CO_T - 1) / Cfg::CO_T, ci_tiles = (g.C + 63) / 64;
     auto kern = tn_taps9_kernel<WCO, WCI, COF, CIF, XF, NST, QROWS, TAB>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (Cfg::NW == 4 && g_t9_lds_pad > Cfg::LDS) ? g_t9_lds_pad : Cfg::LDS) != hipSuccess) {
-            set_error("igemm_tn(taps9): cannot raise dynamic LDS to %d bytes", Cfg::LDS);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done = true;
-    }
-    const int lds = (Cfg::NW == 4 && g_t9_lds_pad > Cfg::LDS) ? g_t9_lds_pad : Cfg::LDS;
-    hipLaunchKernelGGL(kern, dim3(co_tiles * ci_tiles * splits), dim3(64 * Cfg::NW), lds, stream, g, p, q, out, co_tiles, ci_tiles);
+    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), T9_LDS, "igemm_tn(taps9)")) return FRHIP_ELAUNCH;
+    hipLaunchKernelGGL(kern, dim3(co_tiles * ci_tiles * splits), dim3(64 * Cfg::NW), T9_LDS, stream, g, p, q, out, co_tiles, ci_tiles);
     return check_launch("igemm_tn(taps9)");
 }
 
 // rows kernel (14 x 14 maps): K split over whole images, one workgroup per CU beside a forward / data-gradient workgroup (the 82-KB request)
-static int g_t9_rows = getenv("FRHIP_T9_ROWS") ? atoi(getenv("FRHIP_T9_ROWS")) : 1;
 static int tn_rows14_launch(const TnGeom& g, const void* p, const void* q, float* out, int splits, hipStream_t stream,
                             const R14Prev& prev = R14Prev{nullptr, nullptr, 0, 0, 0, 0}) {
+    static_assert(R14::LDS <= T9_LDS, "the slot ring fits the LDS request");
     const int co_tiles = g.Kc / 64, ci_tiles = g.C / 64;
-    const int lds = g_t9_lds_pad > R14::LDS ? g_t9_lds_pad : R14::LDS;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(tn_rows14_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            set_error("igemm_tn(rows14): cannot raise dynamic LDS to %d bytes", lds);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(tn_rows14_kernel, dim3(co_tiles * ci_tiles * splits), dim3(256), lds, stream, g, p, q, out, co_tiles, ci_tiles, prev);
+    if (set_dynamic_lds(reinterpret_cast<const void*>(tn_rows14_kernel), T9_LDS, "igemm_tn(rows14)")) return FRHIP_ELAUNCH;
+    hipLaunchKernelGGL(tn_rows14_kernel, dim3(co_tiles * ci_tiles * splits), dim3(256), T9_LDS, stream, g, p, q, out, co_tiles, ci_tiles, prev);
     return check_launch("igemm_tn(rows14)");
 }
 
 // Sum of K-split slabs, float4 per thread, no atomics (deterministic).  blockIdx.y = g owns slabs g*per_group ..:
 //   final == 0: their sum overwrites the group's first slab (first level of a two-level tree)
 //   final == 1: out[i] += sum (gridDim.y must be 1)
-__device__ __forceinline__ f32x4_t slab_load(const float* p) {
-    if constexpr (TN_SLAB_NT & 2) return __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p));
-    else return *reinterpret_cast<const f32x4_t*>(p);
-}
-
 // At most 32 VGPRs per lane (two accumulators, two loads in flight): the persistent 8-wave linear kernels of the main stream (240 VGPRs, two
 // waves per SIMD) leave exactly 32 registers per lane free on every CU, and with 46 this reduce -- 54 launches per Swin34 step on the side
 // stream -- waited for a whole linear launch to retire every time (47.9 us per launch inside the step against 7.0 us alone).
-#ifndef SLAB_WIDE
-#define SLAB_WIDE 0
-#endif
-#ifndef SLAB_VGPR
-#define SLAB_VGPR 32
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(SLAB_VGPR)))
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(32)))
 void slab_reduce_kernel(float* __restrict__ slabs, int count, int per_group, size_t step, float* __restrict__ out, size_t n4, int final) {
     const int s0 = blockIdx.y * per_group, s1 = min(count, s0 + per_group);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
         f32x4_t a0 = f32x4_t{0.f, 0.f, 0.f, 0.f}, a1 = a0;
         const float* src = slabs + (size_t)s0 * step + i * 4;
         int sp = s0;
-#if SLAB_WIDE        // A/B build (-DSLAB_WIDE=1 -DSLAB_VGPR=64): four loads in flight, 46 registers -- the round-3 kernel
-        f32x4_t a2 = a0, a3 = a0;
-        for (; sp + 4 <= s1; sp += 4) {
-            const f32x4_t v0 = slab_load(src), v1 = slab_load(src + step), v2 = slab_load(src + 2 * step), v3 = slab_load(src + 3 * step);
-            src += 4 * step;
-            a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-        }
-        a0 += a2; a1 += a3;
-#endif
 #pragma unroll 1
         for (; sp + 2 <= s1; sp += 2) {
             const f32x4_t v0 = slab_load(src);
@@ -1078,14 +989,7 @@ static int tn_launch(const TnGeom& g, const void* p, const void* q, float* out, 
     typedef TnTile<T, RB> Tile;
     const int co_tiles = (g.Kc + Tile::BC - 1) / Tile::BC, ci_tiles = (g.C + Tile::BC - 1) / Tile::BC;
     auto kern = tn_kernel<T, RB>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Tile::LDS_BYTES) != hipSuccess) {
-            set_error("igemm_tn: cannot raise dynamic LDS to %d bytes", Tile::LDS_BYTES);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), Tile::LDS_BYTES, "igemm_tn")) return FRHIP_ELAUNCH;
     dim3 grid(co_tiles * ci_tiles * taps * splits);
     hipLaunchKernelGGL(kern, grid, dim3(TN_THREADS), Tile::LDS_BYTES, stream, g, p, q, out, co_tiles, ci_tiles, taps);
     return check_launch("igemm_tn");
@@ -1162,7 +1066,7 @@ static bool t9_applicable(int dtype, int w, int c, int r, int s, int stride, int
 }
 
 static bool r14_applicable(int dtype, int h, int w, int c, int kc, int r, int s, int stride, int pad, long long M, int ldp) {
-    return g_t9_rows && g_t9_narrow && t9_applicable(dtype, w, c, r, s, stride, pad, M, ldp) && h == 14 && w == 14 && (c % 64) == 0 && (kc % 64) == 0;
+    return t9_applicable(dtype, w, c, r, s, stride, pad, M, ldp) && h == 14 && w == 14 && (c % 64) == 0 && (kc % 64) == 0;
 }
 // K split of the rows kernel over images: whole rounds of one workgroup per CU; the epilogue (nine store passes of 36 KB per wave) costs
 // about two images.  Sets g.ksteps (= images) / ksteps_per_split and returns the split count.
@@ -1215,7 +1119,7 @@ static int tn_run(int dtype, const void* p, const void* q, float* out, int n, in
     const size_t out_elems = (size_t)kc * taps * c;
     if (out_elems > 0x7fffffffULL) { set_error("%s: output too large", who); return FRHIP_EINVAL; }
     int rc;
-    // The nine-tap kernel covers every 3x3/s1/p1 bf16 layer (g_tn_taps9: 0 off, 1/2 on); wide = 128-co tiles.
+    // The nine-tap kernel covers every 3x3/s1/p1 bf16 layer (g_tn_taps9: 0 off, 1/2 on).
     if (!xf_scale && ws && r14_applicable(dtype, h, w, c, kc, r, s, stride, pad, M, ldp)) {
         TnGeom gi = g;
         int sp = r14_plan(gi, n, splits);
@@ -1226,10 +1130,8 @@ static int tn_run(int dtype, const void* p, const void* q, float* out, int n, in
         }
     }
     if (t9_applicable(dtype, w, c, r, s, stride, pad, M, ldp)) {
-        const bool wide = kc > 64 && !g_t9_narrow;
-        const int co_t = wide ? 128 : 64;
-        const long long tiles = 1LL * ((kc + co_t - 1) / co_t) * ((c + 63) / 64);
-        const int slots = 256 * ((wide || g_t9_lds_pad > 81920) ? 1 : 2);
+        const long long tiles = 1LL * ((kc + 63) / 64) * ((c + 63) / 64);
+        const int slots = 256;                                                  // one workgroup per CU
         int best = 1; double best_t = 1e30;
         const int max_splits = g.ksteps / 8 > 0 ? g.ksteps / 8 : 1;
         for (int sp = 1; sp <= max_splits && sp <= 1024; ++sp) {
@@ -1243,18 +1145,16 @@ static int tn_run(int dtype, const void* p, const void* q, float* out, int n, in
         g.ksteps_per_split = (g.ksteps + splits - 1) / splits;
         splits = (g.ksteps + g.ksteps_per_split - 1) / g.ksteps_per_split;
         float* dst = tn_pick_dst(g, out, splits, out_elems, ws, ws_bytes);
-        const bool deep = !wide && 64 + 2 * w + 2 <= 128;      // three stages of a 128-row window
+        const bool deep = 64 + 2 * w + 2 <= 128;      // three stages of a 128-row window
         // W <= 14: a 96-row window, 20-KB stages -- FOUR fit the co-resident tile's 82-KB request, so an operand load has three K steps to land
-        const bool deep4 = deep && g_t9_stages4 && 64 + 2 * w + 2 <= 96 && !xf_scale;
-        if (xf_scale) rc = wide ? tn_taps9_launch<2, 4, 4, 1, true>(g, p, q, dst, splits, stream)
-                         : deep ? tn_taps9_launch<1, 4, 4, 1, true, 3, 128>(g, p, q, dst, splits, stream)
+        const bool deep4 = deep && 64 + 2 * w + 2 <= 96 && !xf_scale;
+        if (xf_scale) rc = deep ? tn_taps9_launch<1, 4, 4, 1, true, 3, 128>(g, p, q, dst, splits, stream)
                                 : tn_taps9_launch<1, 4, 4, 1, true>(g, p, q, dst, splits, stream);
-        else if (!wide && g.Ho == g.H && g.Wo == g.W && t9_mask_table(g, stream))
+        else if (g.Ho == g.H && g.Wo == g.W && t9_mask_table(g, stream))
             rc = deep4 ? tn_taps9_launch<1, 4, 4, 1, false, 4, 96, true>(g, p, q, dst, splits, stream)
                : deep ? tn_taps9_launch<1, 4, 4, 1, false, 3, 128, true>(g, p, q, dst, splits, stream)
                       : tn_taps9_launch<1, 4, 4, 1, false, 2, T9_QROWS, true>(g, p, q, dst, splits, stream);
-        else rc = wide ? tn_taps9_launch<2, 4, 4, 1>(g, p, q, dst, splits, stream)
-                : deep4 ? tn_taps9_launch<1, 4, 4, 1, false, 4, 96>(g, p, q, dst, splits, stream)
+        else rc = deep4 ? tn_taps9_launch<1, 4, 4, 1, false, 4, 96>(g, p, q, dst, splits, stream)
                 : deep ? tn_taps9_launch<1, 4, 4, 1, false, 3, 128>(g, p, q, dst, splits, stream)
                        : tn_taps9_launch<1, 4, 4, 1>(g, p, q, dst, splits, stream);
         return rc ? rc : t9_finish(g, out, splits, out_elems, ws, stream);
@@ -1423,14 +1323,7 @@ void head_dw_kernel(const void* __restrict__ dt_ptr, int ldt, const void* __rest
 
 static int head_dw_launch(const void* dt, int ldt, const void* ehat, const void* what, const float* wnorm, float* dw, int n, int classes,
                           float out_scale, hipStream_t stream) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(head_dw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, Hdw::LDS) != hipSuccess) {
-            set_error("frhip_head_dw: cannot raise dynamic LDS to %d bytes", Hdw::LDS);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    if (set_dynamic_lds(reinterpret_cast<const void*>(head_dw_kernel), Hdw::LDS, "frhip_head_dw")) return FRHIP_ELAUNCH;
     hipLaunchKernelGGL(head_dw_kernel, dim3((classes + Hdw::CT - 1) / Hdw::CT), dim3(256), Hdw::LDS, stream, dt, ldt, ehat, (const bf16_t*)what,
                        wnorm, dw, n, classes, (uint32_t)((size_t)n * ldt * 2), (uint32_t)((size_t)n * 512 * 2), out_scale);
     return check_launch("frhip_head_dw");

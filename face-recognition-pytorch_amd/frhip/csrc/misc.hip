@@ -2,6 +2,7 @@
 // PartialFC sampled rows, and the library's error plumbing.  All HBM-bound byte movers.
 #include <stdarg.h>
 #include <stdio.h>
+#include <atomic>
 #include "common.h"
 #include "frhip.h"
 
@@ -23,6 +24,43 @@ int check_launch(const char* what) {
         return FRHIP_ELAUNCH;
     }
     return FRHIP_OK;
+}
+
+// The (kernel, device) pairs whose LDS limit is raised: an open-addressed table of kernel addresses, each with one bit per device.
+// Two threads that race on a first launch may both make the call; it is idempotent.
+int set_dynamic_lds(const void* fn, int bytes, const char* who) {
+    constexpr int SLOTS = 256;
+    static std::atomic<const void*> fns[SLOTS];
+    static std::atomic<uint64_t> devs[SLOTS];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; }
+    const uint64_t bit = (dev >= 0 && dev < 64) ? 1ull << dev : 0;
+    int slot = -1;
+    const size_t h = (size_t)(((uintptr_t)fn >> 4) * 0x9E3779B97F4A7C15ull >> 32);
+    for (int i = 0; i < SLOTS && slot < 0; ++i) {
+        const int s = (int)((h + i) % SLOTS);
+        const void* cur = nullptr;
+        if (fns[s].compare_exchange_strong(cur, fn) || cur == fn) slot = s;
+    }
+    if (slot >= 0 && bit && (devs[slot].load() & bit)) return FRHIP_OK;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+        set_error("%s: cannot raise dynamic LDS to %d bytes", who, bytes);
+        return FRHIP_ELAUNCH;
+    }
+    if (slot >= 0) devs[slot].fetch_or(bit);
+    return FRHIP_OK;
+}
+
+int device_cu_count() {
+    static std::atomic<int> cus[16];               // per device: a process that drives a second GPU sizes its grids for THAT chip
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return 256; }
+    int v = cus[dev].load();
+    if (!v) {
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+        cus[dev].store(v);
+    }
+    return v;
 }
 
 // w[K][RS][C] fp32 -> wt[C][RS][K] T   (data-gradient operand: K-contiguous over output channels)

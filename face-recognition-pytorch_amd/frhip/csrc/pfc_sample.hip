@@ -147,14 +147,7 @@ extern "C" int frhip_pfc_sample(const int64_t* labels, int n, long long class_st
     }
     const int words = (num_local + 31) / 32;
     const int lds = words * 12 + 256 * 4 + 32 * 4;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(pfc_sample_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("frhip_pfc_sample: cannot raise dynamic LDS");
-            return FRHIP_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    if (set_dynamic_lds(reinterpret_cast<const void*>(pfc_sample_kernel), 160 * 1024, "frhip_pfc_sample")) return FRHIP_ELAUNCH;
     hipLaunchKernelGGL(pfc_sample_kernel, dim3(1), dim3(PS_THREADS), lds, stream, labels, n, class_start, num_local, u, num_sample,
                        index_out, rel_out, n_positive);
     return check_launch("frhip_pfc_sample");

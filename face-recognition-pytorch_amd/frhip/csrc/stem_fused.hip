@@ -279,11 +279,8 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__
 // receive from in LDS.
 //   WGRAD = false: partial[block] = { sum d, sum d*(y-mean)*invstd }            (p0 = mean, p1 = invstd)
 //   WGRAD = true : dy = p0*d + p1*y + p2;  slab[block][co][k] = sum dy[co]*col[k]
-#ifndef SF_BWD_OCC
-#define SF_BWD_OCC 2
-#endif
 template <typename T, bool WGRAD>
-__global__ __launch_bounds__(256, SF_BWD_OCC) void stem_bwd_kernel(const float* __restrict__ x, const T* __restrict__ wp,
+__global__ __launch_bounds__(256, 2) void stem_bwd_kernel(const float* __restrict__ x, const T* __restrict__ wp,
                                                        const T* __restrict__ dpool, const uint8_t* __restrict__ argmax,
                                                        const float* __restrict__ p0, const float* __restrict__ p1,
                                                        const float* __restrict__ p2, const float* __restrict__ scale,
@@ -766,14 +763,7 @@ static int sf_fwd(const float* x, const void* wp, const float* scale, const floa
                   int b, int h, int w, hipStream_t stream) {
     const int lds = SF_RH * SF_RW * (64 * (int)sizeof(T) + 16) + 3 * (SF_RH + 2) * (SF_RW + 2) * (int)sizeof(T);
     auto kern = stem_fwd_kernel<T>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            set_error("frhip_stem_fwd: cannot raise dynamic LDS to %d bytes", lds);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "frhip_stem_fwd")) return FRHIP_ELAUNCH;
     hipLaunchKernelGGL(kern, dim3(sf_tiles(b, h, w)), dim3(256), lds, stream, x, (const T*)wp, scale, shift, (T*)pooled, argmax, b, h, w);
     return check_launch("frhip_stem_fwd");
 }
@@ -796,14 +786,7 @@ static int sf_bwd(const float* x, const void* wp, const void* dpool, const uint8
     const int red_bytes = WGRAD ? 4 * 64 * 32 * 4 : 4 * 2 * 64 * 4;
     const int lds = tile_bytes > red_bytes ? tile_bytes : red_bytes;
     auto kern = stem_bwd_kernel<T, WGRAD>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            set_error("%s: cannot raise dynamic LDS to %d bytes", who, lds);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, who)) return FRHIP_ELAUNCH;
     hipLaunchKernelGGL(kern, dim3(frhip_stem_blocks(b, h, w)), dim3(256), lds, stream, x, (const T*)wp, (const T*)dpool, argmax,
                        p0, p1, p2, scale, shift, outbuf, b, h, w);
     return check_launch(who);
@@ -816,14 +799,7 @@ static int sf_bwd2(const float* x, const void* wp, const void* dpool, const uint
     const int lds = WGRAD ? SB_LDS_WGRAD : SB_LDS_REDUCE;
     static_assert(SB_LDS_WGRAD >= SB_WAVES * 64 * 32 * 4 && SB_LDS_WGRAD <= 160 * 1024, "LDS budget");
     auto kern = stem_bwd2_kernel<WGRAD>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            set_error("%s: cannot raise dynamic LDS to %d bytes", who, lds);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, who)) return FRHIP_ELAUNCH;
     hipLaunchKernelGGL(kern, dim3(frhip_stem_blocks(b, h, w)), dim3(SB_THREADS), lds, stream, x, (const bf16_t*)wp,
                        (const bf16_t*)dpool, argmax, p0, p1, p2, scale, shift, outbuf, b, h, w);
     return check_launch(who);

@@ -363,12 +363,8 @@ extern "C" int frhip_winattn_fwd(int dtype, const void* qkv, const float* bias, 
     WaGeom g; g.H = h; g.W = w; g.ws = ws; g.shift = shift; g.n = ws * ws;
     if (dtype == FRHIP_DT_BF16 && g_wa_mfma) return winattn_mfma_fwd(qkv, bias, scale, out, nwin, g, c, heads, stream);
     const int blocks = (nwin * heads + 3) / 4, lds = 4 * wa_per_wave(1) * 4;
-    static bool fattr[2] = {false, false};
-    if (!fattr[dtype]) {
-        const void* fn = dtype == FRHIP_DT_BF16 ? reinterpret_cast<const void*>(winattn_fwd_kernel<bf16_t>) : reinterpret_cast<const void*>(winattn_fwd_kernel<float>);
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) { set_error("frhip_winattn_fwd: LDS %d", lds); return FRHIP_ELAUNCH; }
-        fattr[dtype] = true;
-    }
+    const void* fn = dtype == FRHIP_DT_BF16 ? reinterpret_cast<const void*>(winattn_fwd_kernel<bf16_t>) : reinterpret_cast<const void*>(winattn_fwd_kernel<float>);
+    if (set_dynamic_lds(fn, lds, "frhip_winattn_fwd")) return FRHIP_ELAUNCH;
     if (dtype == FRHIP_DT_BF16)
         hipLaunchKernelGGL(winattn_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), lds, stream, (const bf16_t*)qkv, bias, scale, (bf16_t*)out, nwin, g, c, heads);
     else
@@ -393,12 +389,8 @@ extern "C" int frhip_winattn_bwd(int dtype, const void* qkv, const void* dout, c
         return FRHIP_EINVAL;
     }
     const int lds = 4 * wa_per_wave(2) * 4;
-    static bool attr_done[2] = {false, false};
     const void* fn = dtype == FRHIP_DT_BF16 ? reinterpret_cast<const void*>(winattn_bwd_kernel<bf16_t>) : reinterpret_cast<const void*>(winattn_bwd_kernel<float>);
-    if (!attr_done[dtype]) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) { set_error("frhip_winattn_bwd: LDS %d", lds); return FRHIP_ELAUNCH; }
-        attr_done[dtype] = true;
-    }
+    if (set_dynamic_lds(fn, lds, "frhip_winattn_bwd")) return FRHIP_ELAUNCH;
     if (dtype == FRHIP_DT_BF16)
         hipLaunchKernelGGL(winattn_bwd_kernel<bf16_t>, dim3(heads, chunks), dim3(256), lds, stream, (const bf16_t*)qkv, (const bf16_t*)dout, bias, scale, (bf16_t*)dqkv, workspace, nwin, g, c, heads, wpb);
     else

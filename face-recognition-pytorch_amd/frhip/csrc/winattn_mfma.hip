@@ -518,18 +518,6 @@ __global__ __launch_bounds__(256, 1) void wm_bwd_kernel(const bf16_t* __restrict
 // through LDS, n*n + 97 partial sums stored) that does not depend on how many windows it walked: with 1024 backward workgroups a wave saw four
 // windows and that fixed cost was a third of the launch.  One workgroup per CU (the backward kernel's LDS allows no second one anyway):
 // Swin34 15.93 -> 15.44 ms, AlterNet50 13.11 -> 12.68 ms (same-box A/B over 1024 / 512 / 384 / 256 / 192); forward 4 per CU (-0.05 ms).
-static int wm_cus() {
-    static int cus[16] = {0};                      // per device: a process that drives a second GPU sizes its grids for THAT chip
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return 256; }
-    if (!cus[dev]) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cus[dev] = v;
-    }
-    return cus[dev];
-}
-
 static int wm_chunks(int nwin, int heads, int target_wgs, int* wpb_out) {
     int chunks = (target_wgs + heads - 1) / heads;
     int wpb = (nwin + chunks - 1) / chunks;
@@ -544,18 +532,9 @@ template <int NT>
 static int wm_fwd_launch(const void* qkv, const float* bias, const float* scale, void* out, int nwin, const WaGeom& g, int C,
                          int heads, hipStream_t stream) {
     const int lds = 4 * WM_FWD_WAVE;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(wm_fwd_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            set_error("frhip_winattn_fwd: cannot raise dynamic LDS to %d bytes", lds);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    if (set_dynamic_lds(reinterpret_cast<const void*>(wm_fwd_kernel<NT>), lds, "frhip_winattn_fwd")) return FRHIP_ELAUNCH;
     int wpb;
-    static const int env_fwd = getenv("FRHIP_WA_FWD_WGS") ? atoi(getenv("FRHIP_WA_FWD_WGS")) : 0;
-    const int target = env_fwd ? env_fwd : 4 * wm_cus();
-    const int chunks = wm_chunks(nwin, heads, target, &wpb);
+    const int chunks = wm_chunks(nwin, heads, 4 * device_cu_count(), &wpb);
     hipLaunchKernelGGL(wm_fwd_kernel<NT>, dim3(heads * chunks), dim3(256), lds, stream, (const bf16_t*)qkv, bias, scale, (bf16_t*)out,
                        nwin, g, C, wpb, heads);
     return check_launch("frhip_winattn_fwd");
@@ -576,18 +555,9 @@ static int wm_bwd_launch(const void* qkv, const void* dout, const float* bias, c
                          float* dscale, const WaColsum& colsum, int nwin, const WaGeom& g, int C, int heads, float* ws, size_t ws_bytes,
                          hipStream_t stream) {
     const int lds = 4 * WM_BWD_WAVE + 16 * 64 * 16;                  // + the head's bias tile in the score layout
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(wm_bwd_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            set_error("frhip_winattn_bwd: cannot raise dynamic LDS to %d bytes", lds);
-            return FRHIP_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    if (set_dynamic_lds(reinterpret_cast<const void*>(wm_bwd_kernel<NT>), lds, "frhip_winattn_bwd")) return FRHIP_ELAUNCH;
     int wpb;
-    static const int env_bwd = getenv("FRHIP_WA_BWD_WGS") ? atoi(getenv("FRHIP_WA_BWD_WGS")) : 0;
-    const int target = env_bwd ? env_bwd : wm_cus();
-    const int chunks = wm_chunks(nwin, heads, target, &wpb);
+    const int chunks = wm_chunks(nwin, heads, device_cu_count(), &wpb);
     if (!ws || (size_t)heads * chunks * WA_PART * sizeof(float) > ws_bytes) {
         set_error("frhip_winattn_bwd: the workspace must hold %d partial-sum slots of %d floats", heads * chunks, WA_PART);
         return FRHIP_EINVAL;

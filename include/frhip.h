@@ -45,7 +45,8 @@ typedef void* frhip_stream_t;
  * The frhip_set_* functions are TEST / TUNING HOOKS, not part of that contract: they flip process-global kernel-selection
  * switches (which tile, which kernel variant -- never the arithmetic contract beyond what each hook documents), are not
  * synchronised, and must only be called while no other thread is inside the library.  The product path (nets/, model/,
- * bench.py) never changes them (one read-only query, frhip_set_winattn_mfma(-1)); the defaults are the measured-best settings (environment overrides are read once, at load). */
+ * bench.py) never changes them (one read-only query, frhip_set_winattn_mfma(-1)); the defaults are the measured-best settings, and the
+ * library reads no environment variables. */
 const char* frhip_last_error(void);
 int frhip_abi_version(void);
 /* stream-concurrency probe: one wave that occupies `stream`'s hardware queue for `ticks` of the 100-MHz wall clock (<= 1e8).

@@ -33,13 +33,12 @@ hdr_a = ("# AlterNet50 @192 with the fp8 forward path (BASELINE cfg 5), one trai
          "# rocprofv3 --kernel-trace -- python3 bench.py --network AlterNet50 --fp8 --steps 6 --warmup 3 --no-cpu-baseline ; tools/trace_summary.py\n")
 open(os.path.join(P, TAG + "_final_alternet50_fp8_step_anatomy.txt"), "w").write(hdr_a + open(os.path.join(F, "alt_step_anatomy.txt")).read())
 # MFMA utilisation counters of the dominant kernels (tools/pmc_run.sh: one rocprofv3 --pmc pass per counter group, kernel-trace only)
-have_pmc = any(os.path.exists(os.path.join(F, "pmc_%s.txt" % w)) for w in ("fwd", "dgrad", "wgrad", "wgrad8"))
+have_pmc = any(os.path.exists(os.path.join(F, "pmc_%s.txt" % w)) for w in ("fwd", "dgrad", "wgrad"))
 with open(os.path.join(P, TAG + "_pmc_mfma_util.txt") if have_pmc else os.devnull, "w") as out:       # QUICK=1 runs keep the committed counters
     out.write("# rocprofv3 --pmc <group> --kernel-trace -- python3 tools/pmc_one.py fwd|dgrad|wgrad 14 256 256   (B = 512, 256-channel 14x14 layer, bf16)\n"
               "# groups: tools/pmc_run.sh.  MFMA utilisation = SQ_VALU_MFMA_BUSY_CYCLES / SQ_BUSY_CU_CYCLES / 4 (four SIMDs per CU).\n"
-              "# wgrad = the 4-wave co-resident kernel the step uses (14 x 14: tn_rows14_kernel, 32x32x16 MFMAs of which 14 of 16 K slots carry pixels);\n"
-              "# wgrad8 = the 8-wave pixel-stream tile (FRHIP_T9_NARROW=0; the stand-alone-fastest choice until round 4).\n")
-    for what in ("fwd", "dgrad", "wgrad", "wgrad8"):
+              "# wgrad = the 4-wave co-resident kernel the step uses (14 x 14: tn_rows14_kernel, 32x32x16 MFMAs of which 14 of 16 K slots carry pixels).\n")
+    for what in ("fwd", "dgrad", "wgrad"):
         f = os.path.join(F, "pmc_%s.txt" % what)
         if not os.path.exists(f):
             continue

@@ -1,5 +1,5 @@
 """Build named variants of ONE translation unit with extra -D flags (linked against the other objects of libfrhip.so):
-    python tools/variants.py bn "u4:-DEW_UNROLL=4" "r16:-DEW_ROWS=16"
+    python tools/variants.py bn "a:-DNAME=1" "b:-DNAME=2"
 -> face-recognition-pytorch_amd/frhip/build/var/libfrhip_<unit>_<name>.so ; run anything with FRHIP_LIB_PATH=<that file>."""
 import os
 import subprocess
