@@ -7,6 +7,7 @@ folds torch.nn.utils.clip_grad_norm_(params, max_norm) (/root/reference/model/FR
 Parameters the kernels cannot take (non-CUDA, non-fp32, sparse, strided differently from their gradient) or options
 they do not implement (nesterov, dampening, maximize) make the whole step fall back to torch's own implementation."""
 import ctypes
+import weakref
 
 import numpy as np
 import torch
@@ -16,6 +17,33 @@ from ._abi import check, lib
 
 CHUNK = 65536
 _CHUNK_DT = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("n", "<u4"), ("group", "<u4")])
+
+
+# Side-stream work parked to run UNDER the backbone's backward pass, at a point the backbone chooses: the PartialFC head parks its early
+# parameter update here (1.25 GB of HBM traffic at 122 000 classes).  Launched right away it collides with the backbone's tail -- a chain of
+# a dozen small, latency-bound kernels (bn3 / fc / bn2 backward) whose every load then queues behind a saturated memory system; a few
+# blocks later the main stream runs MFMA-bound 512-channel convolutions that do not mind.
+# Entries are (owner optimizer, the owner's step token when parked, launch): an entry whose owner has since begun another step (zero_grad()
+# bumps the token) or was collected is dropped, never launched -- a closure parked by a backward pass that did not reach a frhip backbone
+# (frozen / foreign encoder, exception) cannot fire on a later step's gradients or under another model's backward pass.
+DEFERRED_SIDE = []
+
+
+def park_deferred(owner, launch):
+    del DEFERRED_SIDE[:]                  # at most one parked update
+    DEFERRED_SIDE.append((weakref.ref(owner), getattr(owner, "_frhip_step_token", 0), launch))
+
+
+def run_deferred_side():
+    while DEFERRED_SIDE:
+        ref, token, launch = DEFERRED_SIDE.pop(0)
+        owner = ref()
+        if owner is not None and getattr(owner, "_frhip_step_token", 0) == token:
+            launch()
+
+
+def drop_deferred(owner):
+    DEFERRED_SIDE[:] = [e for e in DEFERRED_SIDE if e[0]() is not None and e[0]() is not owner]
 
 
 class _Group(ctypes.Structure):
@@ -160,8 +188,7 @@ class SGD(torch.optim.SGD):
         self._early = {}
         # a head update still parked for a backward pass that never reached a frhip backbone belongs to the step that ends here
         self._frhip_step_token = getattr(self, "_frhip_step_token", 0) + 1
-        from nets import _backbone as _bb
-        _bb.drop_deferred(self)
+        drop_deferred(self)
         return super().zero_grad(set_to_none=set_to_none)
 
     def _fallback(self, clip, done=()):

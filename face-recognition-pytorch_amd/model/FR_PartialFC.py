@@ -17,7 +17,7 @@ import torch
 from torch import nn
 from torch.nn.parallel import DistributedDataParallel as DDP
 
-import nets._backbone as _bb
+from frhip.optim import run_deferred_side
 
 
 class _NormalizeFn(torch.autograd.Function):
@@ -112,7 +112,7 @@ class Model(nn.Module):
         loss.backward()
         # an early head update the backbone's backward pass did not get to launch (the hook fired behind it): launch it now, so that
         # nothing parked survives into the next step
-        _bb.run_deferred_side()
+        run_deferred_side()
         if hasattr(self.opt, "last_grad_norm"):          # frhip.optim.SGD: the clip rides inside the fused update
             self.opt.step(clip=(self.encoder.parameters(), 5))
         else:

@@ -38,9 +38,6 @@ import os
 # test hook: take the multi-rank branch (all-gather, all-reduces, reduce-scatter) even in a 1-rank group, so the
 # RCCL call sequence can be exercised on a single-GPU box
 _FORCE_COLLECTIVES = os.environ.get("FRHIP_FORCE_COLLECTIVES", "0") == "1"
-_PFC_SAMPLE_KERNEL = os.environ.get("FRHIP_PFC_SAMPLE_KERNEL", "1") == "1"
-_EARLY_HEAD_UPDATE = os.environ.get("FRHIP_EARLY_HEAD_UPDATE", "1") == "1"
-_HEAD_DW_FUSED = os.environ.get("FRHIP_HEAD_DW_FUSED", "1") == "1"       # 0: class-centre gradient as GEMM + normalise-backward pass
 
 
 # --------------------------------------------------------------------------------------------- kernels
@@ -87,9 +84,10 @@ class HipHeadKernels:
         d_e = ops.l2norm_bwd(d_eh, ehat, enorm, out_scale=e_scale)
         if on_de is not None:
             on_de(d_e)
-        d_w = ops.head_dw(dt, ehat, what, wnorm) if _HEAD_DW_FUSED else None      # GEMM + normalise-backward in one launch (bf16, d = 512)
+        d_w = ops.head_dw(dt, ehat, what, wnorm)       # GEMM + normalise-backward in one launch (bf16, d = 512; 289 -> 191 us at 122 000 classes)
         if d_w is not None:
             return d_e, d_w
+        # shapes head_dw does not serve: GEMM, then normalise-backward
         d_wh = torch.empty((classes, d), dtype=torch.float32, device=ehat.device)
         ops.gemm_tn(dt, ehat, d_wh, kc=classes, overwrite=True)      # 250 MB at 122 000 classes: stored once, never zero-filled
         return d_e, ops.l2norm_bwd(d_wh, what, wnorm)
@@ -349,7 +347,7 @@ class _PartialFCBase(torch.nn.Module):
     def _sample_kernel_ok(self, dev):
         """one launch of frhip_pfc_sample (csrc/pfc_sample.hip) instead of the ~25 torch launches of the label side"""
         k = self.kernels
-        return (_PFC_SAMPLE_KERNEL and dev.type == "cuda" and getattr(k, "pfc_sample", None) is not None
+        return (dev.type == "cuda" and getattr(k, "pfc_sample", None) is not None
                 and self.num_local <= k.pfc_sample_max_local())
 
     def _draw_perm(self, dev):
@@ -536,9 +534,9 @@ class _PartialFCBase(torch.nn.Module):
         (1.25 GB of HBM traffic at 122 000 classes) is then launched from a post-accumulate-grad hook on the weight-gradient side
         stream and runs beside the backbone's backward; step() skips the group.  Same kernel, same arithmetic, only earlier.
         ONE-SHOT: the hook disarms itself, so a backward() that is not followed by step() (gradient accumulation, inspection)
-        never changes a parameter.  FRHIP_EARLY_HEAD_UPDATE=0 turns it off."""
+        never changes a parameter."""
         p = self.weight_activated
-        if not _EARLY_HEAD_UPDATE or optimizer is None or not hasattr(optimizer, "step_group_early") or not p.is_cuda:
+        if optimizer is None or not hasattr(optimizer, "step_group_early") or not p.is_cuda:
             return
         self._early_armed = optimizer
         if getattr(p, "_frhip_early_hook", None) is not None:
@@ -550,14 +548,12 @@ class _PartialFCBase(torch.nn.Module):
                 return
             if opt.param_groups[-1]["params"][0] is not param or torch.cuda.is_current_stream_capturing():
                 return
-            from . import _backbone as bb
+            from frhip.optim import park_deferred
+            from ._backbone import side_stream
 
             def launch():
-                opt.step_group_early(len(opt.param_groups) - 1, bb.side_stream(param.device))
-            if bb.DEFER_EARLY_BLOCKS >= 0:
-                bb.park_deferred(opt, launch)      # the backbone's backward pass launches it a few blocks in (or its join() does)
-            else:
-                launch()
+                opt.step_group_early(len(opt.param_groups) - 1, side_stream(param.device))
+            park_deferred(opt, launch)      # the backbone's backward pass launches it a few blocks in (or its join() does)
 
         p._frhip_early_hook = p.register_post_accumulate_grad_hook(hook)
 

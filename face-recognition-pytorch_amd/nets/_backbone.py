@@ -10,42 +10,34 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from frhip import ops
+from frhip.optim import DEFERRED_SIDE, run_deferred_side  # noqa: F401  (DEFERRED_SIDE: the same list under its former name here)
 
 _OVERLAP_WGRAD = os.environ.get("FRHIP_OVERLAP_WGRAD", "1") == "1"
-# consecutive 3x3 weight gradients on 14 x 14 maps as a chain: each launch sums its predecessor's K-split slabs in its prologue (no reduce
-# launch between them; ops.conv_wgrad_chain).  0 (default): every weight gradient followed by its own reduce launch.  Measured, ResNet50 step,
-# one box, alternating: 23.71 ms without / 23.85 with (and 23.85 / 24.24 with the hand-over behind the data-gradient, FRHIP_WGRAD_LATE_MAXC=256).
+# every weight gradient is followed by its own reduce launch.  Chaining the 3x3 weight gradients on 14 x 14 maps (each launch sums its
+# predecessor's K-split slabs in its prologue, ops.conv_wgrad_chain) was measured slower and dropped: ResNet50 step, one box, alternating,
+# 23.71 ms without / 23.85 with (and 23.85 / 24.24 with the hand-over behind the data-gradient up to 256 channels).
 # The reduce launch (8 us alone, 50 - 65 us beside the main stream, which keeps the CUs' register files full) delays the next weight
 # gradient so that it runs beside the HBM-bound BatchNorm-backward pass instead of beside the whole data-gradient: the chain removes 27
 # launches and 1.4 ms of side-queue time and the main stream's convolutions slow down by more (in-step conv launch 145 -> 154 us).
-_WGRAD_CHAIN = os.environ.get("FRHIP_WGRAD_CHAIN", "0") == "1"
-_STEM_FUSED_REDUCE = os.environ.get("FRHIP_STEM_FUSED_REDUCE", "1") == "1"     # 0: the stem's own recompute reduction pass
-# bn1-apply + ReLU folded into conv2's operand path (forward and weight gradient; the activated tensor is never written).
-# Built, bit-identical to the separate pass, and OFF by default: measured on the ResNet50 step (B = 512, same box, two A/B
-# rounds) 29.5 ms fused vs 28.8 ms separate.  The in-LDS transform is ~3.5 VALU operations per element in kernels whose
-# matrix pipe already waits on instruction issue; it costs more (+15 us per forward conv2, +20 us per weight gradient) than
-# the 23-91 us HBM pass it removes wherever that pass is short, and the long passes (64 channels) sit on the layers whose
-# weight-gradient K step is shortest.  DESIGN.md section 4.8.
-# 0: a1 = relu(bn1(y1)) is a pass of its own.  1: folded into conv2's forward AND weight-gradient kernels (a1 never exists).
-# 2: folded into the forward kernel only; the backward pass re-forms a1 with a BatchNorm-apply pass on the SIDE stream right in front
-#    of conv2's weight gradient, where it hides beside the main stream's matrix work (the forward pass has nothing to hide it under)
-# 3 (default since the lean store epilogue, round 3): conv2's forward kernel forms a1 = relu(bn1(y1)) in LDS from y1 and writes it out on the
-# way -- no BatchNorm-apply launch for bn1 in the forward pass, bit-identical tensors (-0.23 ms per step, three alternating pairs of
-# 40-step runs on one box: 24.58 / 24.49 / 24.45 -> 24.28 / 24.31 / 24.21).  0: separate pass.  1 / 2: a1 never written (slower).
-# FRHIP_FUSE_BN1_CH: comma list of channel widths mode 3 applies to (default: all)
-_FUSE_BN1 = int(os.environ.get("FRHIP_FUSE_BN1", "3"))
-_FUSE_BN1_CH = [int(v) for v in os.environ.get("FRHIP_FUSE_BN1_CH", "").split(",") if v]
-# inference: eval-mode BatchNorms folded into the store epilogues of the convolutions (0: separate BatchNorm-apply passes)
-_EVAL_FOLD = os.environ.get("FRHIP_EVAL_FOLD", "1") == "1"
+_STEM_FUSED_REDUCE = True     # test hook; False: the stem's own recompute reduction pass
+# True (default since the lean store epilogue, round 3): conv2's forward kernel forms a1 = relu(bn1(y1)) in LDS from y1 and writes it
+# out on the way -- no BatchNorm-apply launch for bn1 in the forward pass, bit-identical tensors (-0.23 ms per step, three alternating
+# pairs of 40-step runs on one box: 24.58 / 24.49 / 24.45 -> 24.28 / 24.31 / 24.21).  False (test hook; also wherever
+# ops.conv_bnrelu_fusable says no): a1 is a BatchNorm-apply pass of its own.
+# Never writing a1 (bn1-apply + ReLU folded into conv2's forward AND weight-gradient kernels, or re-formed on the side stream for the
+# weight gradient) was measured slower and dropped: 29.5 ms fused vs 28.8 ms separate (ResNet50 step, B = 512, same box, two A/B rounds).
+# The in-LDS transform is ~3.5 VALU operations per element in kernels whose matrix pipe already waits on instruction issue; in the
+# weight gradient it costs more (+20 us per launch) than the 23-91 us HBM pass it removes wherever that pass is short.  DESIGN.md 4.8.
+_FUSE_BN1 = True
+# test hook: inference with the eval-mode BatchNorms folded into the store epilogues of the convolutions (False: separate BatchNorm-apply passes)
+_EVAL_FOLD = True
 # hand a weight gradient to the side stream BEFORE the data-gradient of the same dy is enqueued (the side stream waits for what
 # the main stream holds at the hand-over): 27.16 -> 26.9 ms on the ResNet50 step.  One hand-over per block instead of one per
-# weight gradient (fewer barrier packets, but conv2's weight gradient starts a data-gradient later) measured 27.3 -> 27.7: off.
-_WGRAD_EARLY = os.environ.get("FRHIP_WGRAD_EARLY", "1") == "1"
-_STEM_GRAM = os.environ.get("FRHIP_STEM_GRAM", "1") == "1"       # stem weight gradient from the Gram matrix of the input (no conv recompute)
+# weight gradient (fewer barrier packets, but conv2's weight gradient starts a data-gradient later) measured 27.3 -> 27.7: removed.
 # ... except for layers of at most this many channels, whose weight gradient is handed over BEHIND the data-gradient that reads the
-# same dy (experiment: on the wide early maps the BatchNorm-backward pass in front of each data-gradient is long and HBM-bound,
-# and a weight gradient that starts with the data-gradient is done before the next such pass begins)
-_WGRAD_LATE_MAXC = int(os.environ.get("FRHIP_WGRAD_LATE_MAXC", "64"))   # same-box A/B, two rounds: 26.15 / 26.13 (0) -> 26.06 / 26.04 (64), 26.11 / 26.16 (128), 26.40 / 26.37 ms (256)
+# same dy (on the wide early maps the BatchNorm-backward pass in front of each data-gradient is long and HBM-bound, and a weight
+# gradient that starts with the data-gradient is done before the next such pass begins)
+_WGRAD_LATE_MAXC = 64   # same-box A/B, two rounds: 26.15 / 26.13 (0) -> 26.06 / 26.04 (64), 26.11 / 26.16 (128), 26.40 / 26.37 ms (256)
 _DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp32": torch.float32, "float32": torch.float32}
 
 
@@ -166,9 +158,6 @@ _PREBUILT_ARENA = {}
 _SIDE_STREAMS = {}
 
 
-_PROBE_STREAMS = os.environ.get("FRHIP_PROBE_STREAMS", "1") == "1"
-
-
 def _runs_beside(main, cand, ticks=50000):
     """True when a kernel on `cand` and a kernel on `main` execute at the same time (two 0.5-ms single-wave spins take about as
     long as one), False when the two streams share a hardware queue and serialise.  The first launch on a new stream creates its
@@ -207,50 +196,20 @@ def side_stream(device):
         if torch.cuda.is_current_stream_capturing():              # no timing inside a graph capture: streams are graph branches there
             _SIDE_STREAMS[key] = tried[0]
             return tried[0]
-        if _PROBE_STREAMS:
-            while not _runs_beside(main, tried[-1]) and len(tried) < 12:
-                tried.append(torch.cuda.Stream(device=device))
-            if not _runs_beside(main, tried[-1]):
-                import warnings
-                warnings.warn("frhip: no side stream runs concurrently with the main stream (all share its hardware queue); "
-                              "weight gradients will not overlap -- raise GPU_MAX_HW_QUEUES")
-                tried = tried[:1]
-        if os.environ.get("FRHIP_DEBUG_STREAMS"):
-            print("frhip: side stream = candidate %d of %d probed" % (len(tried), len(tried)), flush=True)
+        while not _runs_beside(main, tried[-1]) and len(tried) < 12:
+            tried.append(torch.cuda.Stream(device=device))
+        if not _runs_beside(main, tried[-1]):
+            import warnings
+            warnings.warn("frhip: no side stream runs concurrently with the main stream (all share its hardware queue); "
+                          "weight gradients will not overlap -- raise GPU_MAX_HW_QUEUES")
+            tried = tried[:1]
         _SIDE_STREAMS[key] = tried[-1]
         _SIDE_STREAMS[(key[0], "rejected", key[1])] = tried[:-1]      # keep them alive: later candidates get other queues
     return _SIDE_STREAMS[key]
 
 
-# Side-stream work that does not belong to the backbone but should run UNDER its backward pass, at a point the backbone chooses: the
-# PartialFC head parks its early parameter update here (1.25 GB of HBM traffic at 122 000 classes).  Launched right away it collides with
-# the backbone's tail -- a chain of a dozen small, latency-bound kernels (bn3 / fc / bn2 backward) whose every load then queues behind a
-# saturated memory system; a few blocks later the main stream runs MFMA-bound 512-channel convolutions that do not mind.
-# Entries are (owner optimizer, the owner's step token when parked, launch): an entry whose owner has since begun another step (zero_grad()
-# bumps the token) or was collected is dropped, never launched -- a closure parked by a backward pass that did not reach a frhip backbone
-# (frozen / foreign encoder, exception) cannot fire on a later step's gradients or under another model's backward pass.
-DEFERRED_SIDE = []
-
-
-def park_deferred(owner, launch):
-    import weakref
-    del DEFERRED_SIDE[:]                  # at most one parked update
-    DEFERRED_SIDE.append((weakref.ref(owner), getattr(owner, "_frhip_step_token", 0), launch))
-
-
-def run_deferred_side():
-    while DEFERRED_SIDE:
-        ref, token, launch = DEFERRED_SIDE.pop(0)
-        owner = ref()
-        if owner is not None and getattr(owner, "_frhip_step_token", 0) == token:
-            launch()
-
-
-def drop_deferred(owner):
-    DEFERRED_SIDE[:] = [e for e in DEFERRED_SIDE if e[0]() is not None and e[0]() is not owner]
-
-
-DEFER_EARLY_BLOCKS = int(os.environ.get("FRHIP_EARLY_HEAD_DEFER", "2"))      # blocks of the backward pass to let go by (-1: launch at once)
+# blocks of the backward pass to let go by before the side-stream work parked in frhip.optim (the head's early update) is launched
+DEFER_EARLY_BLOCKS = 2        # 4 measured no faster
 
 
 class BackwardCtx:
@@ -279,7 +238,6 @@ class BackwardCtx:
         self.reduced_from = self.flat.numel()          # arena[reduced_from:] has been handed to RCCL
         self.works = []
         self.before_join = []                          # deferred gradient work (e.g. the batched position-bias backward)
-        self._chain, self._chain_flip = None, 0        # pending link of the chained 14 x 14 weight gradients (ops.conv_wgrad_chain)
 
     def G(self, p):
         return self.grads[p]
@@ -294,41 +252,12 @@ class BackwardCtx:
         with torch.cuda.stream(self.side):
             fn()
 
-    def wgrad(self, dy, x, gview, r, s, stride, pad, bnrelu=None):
-        """bnrelu = BN state: x is the INPUT of a BatchNorm + ReLU whose output (the convolution's real operand) was never
-        materialised; the weight-gradient kernel re-forms it in LDS"""
-        if bnrelu is not None and _FUSE_BN1 == 2:
-            fn = lambda: ops.conv_wgrad(dy, ops.bn_apply(x, bnrelu, relu=True), gview, r, s, stride, pad)      # noqa: E731
-        elif bnrelu is not None:
-            fn = lambda: ops.conv_wgrad_bnrelu(dy, x, bnrelu, gview, r, s, stride, pad)       # noqa: E731
-        elif _WGRAD_CHAIN and ops.conv_wgrad_chain_ok(dy, x, r, s, stride, pad):
-            fn = lambda: self._chain_link(dy, x, gview)                                       # noqa: E731
-        else:
-            fn = lambda: ops.conv_wgrad(dy, x, gview, r, s, stride, pad)                      # noqa: E731
-        self.on_side(fn, dy, x, gview, bnrelu)
-
-    def _chain_link(self, dy, x, gview):
-        """one link of the chain of 14 x 14 weight gradients (ops.conv_wgrad_chain): the previous link's K-split slabs are summed in this
-        launch's prologue; runs on the weight-gradient stream"""
-        bufs = ops.chain_slabs(x.device)
-        self._chain = ops.conv_wgrad_chain(dy, x, gview, bufs[self._chain_flip], self._chain)
-        self._chain_flip ^= 1
-
-    def flush_chain(self):
-        """the last link's slabs, with the ordinary reduce launches (on the weight-gradient stream, before anyone reads the gradients)"""
-        if self._chain is None:
-            return
-        link, self._chain = self._chain, None
-        if self.side is None:
-            ops.conv_wgrad_chain_finish(link)
-        else:
-            with torch.cuda.stream(self.side):
-                ops.conv_wgrad_chain_finish(link)
+    def wgrad(self, dy, x, gview, r, s, stride, pad):
+        self.on_side(lambda: ops.conv_wgrad(dy, x, gview, r, s, stride, pad), dy, x, gview)
 
     def _reduce(self, lo, hi):
         if hi <= lo:
             return
-        self.flush_chain()                              # the slice must be final: the last chained weight gradient still owes its reduce
         chunk = self.flat[lo:hi]
         # RCCL averages in the collective; other backends (gloo in tests) sum and join() scales
         op = dist.ReduceOp.AVG if dist.get_backend() == "nccl" else dist.ReduceOp.SUM
@@ -355,7 +284,8 @@ class BackwardCtx:
             self.reduced_from = lo
 
     def run_deferred(self):
-        """launch the side-stream work other modules parked for the backward pass (DEFERRED_SIDE: the head's early parameter update)"""
+        """launch the side-stream work other modules parked for the backward pass (frhip.optim.DEFERRED_SIDE: the head's early
+        parameter update)"""
         run_deferred_side()
 
     def join(self):
@@ -363,7 +293,6 @@ class BackwardCtx:
         for fn in self.before_join:
             fn()
         self.before_join = []
-        self.flush_chain()
         if self.allreduce:
             self._reduce(0, self.reduced_from)
             self.reduced_from = 0
@@ -428,9 +357,6 @@ def bn_forward_state(bn, part, count, training):
     return ops.bn_eval_affine(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, bn.eps)
 
 
-_FUSED_STEM = os.environ.get("FRHIP_FUSED_STEM", "1") == "1"
-
-
 def stem_forward(net, x, training, sv):
     """conv3x3(3->64) - BN - ReLU - MaxPool(3,2,1) -> NHWC [B, H/2, W/2, 64].
 
@@ -440,7 +366,7 @@ def stem_forward(net, x, training, sv):
     dt = net.dtype
     b, _, h, w = x.shape
     stride = net.conv1.stride
-    if stride == 1 and _FUSED_STEM:
+    if stride == 1:
         wp0 = ops.pack_stem(net.conv1.physical().reshape(64, 27), dt, kp=32)
         if training:
             st0 = bn_forward_state(net.bn1, ops.stem_stats(x, wp0), b * h * w, True)
@@ -450,7 +376,7 @@ def stem_forward(net, x, training, sv):
         if sv is not None:
             sv.x0, sv.wp0, sv.st0, sv.arg0, sv.col, sv.p0 = x, wp0, st0, arg0, None, cur
             sv.gram = None
-            if training and _STEM_GRAM:
+            if training:
                 # the data-only part of the stem's weight gradient (csrc/stem_algebra.hip) needs x alone: it runs on the side stream
                 # under the forward pass, and the backward pass then needs no recompute of the 112 x 112 x 64 conv map
                 side = side_stream(x.device) if _OVERLAP_WGRAD else None
@@ -584,15 +510,11 @@ def basic_block_forward(blk, xin, dt, training, save, wprep=None, q8=None):
     if f1:
         a1, a18 = ops.bn_apply_q8(y1, st1, relu=True)
         y2, p2 = ops.conv_fwd_fp8(a18, *q8.packs[blk.conv2], blk.stride, 1, want_stats=training)
-    elif _FUSE_BN1 == 3 and (not _FUSE_BN1_CH or y1.shape[3] in _FUSE_BN1_CH) and ops.conv_bnrelu_fusable(y1, w2, blk.stride, 1):
+    elif _FUSE_BN1 and ops.conv_bnrelu_fusable(y1, w2, blk.stride, 1):
         # conv2 forms a1 = relu(bn1(y1)) in LDS from y1 and writes it out on the way (the backward pass reads it): no BatchNorm-apply
         # launch, no second read of y1, the backward pass unchanged
         a1 = torch.empty_like(y1) if save else None
         y2, p2 = ops.conv_fwd_bnrelu(y1, st1, w2, blk.stride, 1, want_stats=training, act_out=a1)
-    elif _FUSE_BN1 in (1, 2) and ops.conv_bnrelu_fusable(y1, w2, blk.stride, 1):
-        # a1 = relu(bn1(y1)) is never written: conv2 (and, in the backward pass, its weight gradient) form it in LDS from y1
-        a1 = None
-        y2, p2 = ops.conv_fwd_bnrelu(y1, st1, w2, blk.stride, 1, want_stats=training)
     else:
         a1 = ops.bn_apply(y1, st1, relu=True)
         y2, p2 = ops.conv_fwd(a1, w2, blk.stride, 1, want_stats=training)
@@ -642,14 +564,11 @@ def basic_block_backward(blk, s, dout, dt, bc, part2=None, next_bn=None):
     w2t = s.w2t if getattr(s, "w2t", None) is not None else ops.pack_wt(blk.conv2.physical(), dt)
     # the BN1 (+ReLU) backward reduction over (da1, y1) rides in the epilogue of conv2's data-gradient
     def wgrad2():
-        if s.a1 is None:    # bn1 + ReLU were folded into conv2's operand path: the weight gradient re-forms a1 from y1 as well
-            bc.wgrad(dy2, s.y1, phys_grad(G(blk.conv2.weight)), 3, 3, blk.stride, 1, bnrelu=s.st1)
-        else:
-            bc.wgrad(dy2, s.a1, phys_grad(G(blk.conv2.weight)), 3, 3, blk.stride, 1)
+        bc.wgrad(dy2, s.a1, phys_grad(G(blk.conv2.weight)), 3, 3, blk.stride, 1)
     # the side stream waits for what the main stream has enqueued at the moment of the hand-over: hand a weight gradient
     # over as soon as its operands are enqueued, i.e. BEFORE the data-gradient that reads the same dy
-    early2 = _WGRAD_EARLY and dy2.shape[3] > _WGRAD_LATE_MAXC
-    early1 = _WGRAD_EARLY and s.x.shape[3] > _WGRAD_LATE_MAXC
+    early2 = dy2.shape[3] > _WGRAD_LATE_MAXC
+    early1 = s.x.shape[3] > _WGRAD_LATE_MAXC
     if early2:
         wgrad2()
     da1, part1 = ops.conv_dgrad(dy2, w2t, s.y1.shape, 3, 3, blk.stride, 1, bnred=(s.y1, s.st1, True))

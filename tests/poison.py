@@ -75,14 +75,14 @@ def assert_poison_applies(pattern, dtype, device="cuda"):
 def reset_frhip_caches():
     """drop every module-level device-buffer cache of frhip / nets, so that the next call allocates it again through torch.empty (under
     an active poisoned_empty: filled with the pattern).  Caches of host-side facts (shape predicates, side streams, carving plans) stay."""
-    from frhip import ops
+    from frhip import ops, optim
     ops._WORKSPACES.clear()          # split-K workspace (slabs of the weight-gradient GEMMs, gemm_nt_splitk)
     ops._CHAIN_SLABS.clear()         # slab pair of the chained 14 x 14 weight gradients
     ops._WPREP.clear()               # arena of the per-step bf16 weight packs + its pointer table
     ops._Q8W.clear()                 # fp8 weight packs + scales
+    del optim.DEFERRED_SIDE[:]       # head update parked for a backward pass
     try:
         from nets import _backbone
     except ImportError:
         return
     _backbone._PREBUILT_ARENA.clear()    # gradient arena carved during the forward pass (zero-filled, but dropped all the same)
-    del _backbone.DEFERRED_SIDE[:]

@@ -61,6 +61,26 @@ def test_sgd_falls_back_to_torch_on_cpu_tensors():
         assert torch.equal(x, y)
 
 
+def test_zero_grad_drops_the_parked_update_without_nets(monkeypatch):
+    """frhip.optim keeps the side-stream work parked for a backbone's backward pass (the PartialFC head's early update).  zero_grad()
+    begins a new step and drops its optimizer's parked entry, with no import of the nets package above frhip (the reference tree has a
+    nets package of its own)."""
+    monkeypatch.setitem(sys.modules, "nets", None)
+    from frhip import optim
+    ran = []
+    p = torch.nn.Parameter(torch.ones(4))
+    p.grad = torch.ones(4)
+    opt = optim.SGD([p], lr=0.1, momentum=0.9)
+    optim.park_deferred(opt, lambda: ran.append("same step"))
+    optim.run_deferred_side()
+    assert ran == ["same step"]
+    optim.park_deferred(opt, lambda: ran.append("stale"))
+    opt.zero_grad()
+    optim.run_deferred_side()
+    assert ran == ["same step"] and not optim.DEFERRED_SIDE
+    assert p.grad is None
+
+
 @pytest.mark.gpu
 def test_sgd_matches_torch_sgd_and_clip_grad_norm():
     from frhip import optim as _o
