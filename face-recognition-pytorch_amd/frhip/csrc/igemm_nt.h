@@ -466,6 +466,18 @@ __device__ __forceinline__ void epi_stats_tail_mfma(const float (&a1)[4], const 
     }
 }
 
+// The 16-byte buffer store of the epilogues below, with the row offset folded into voffset and soffset 0.  A store of more than 8 bytes
+// reads its data registers after it issues, so a VALU write to them right behind it must wait a state.  The ISA's wait-state table
+// exempts buffer stores whose soffset is an SGPR, and LLVM's hazard recognizer follows it: with the row step as SGPR soffset it padded no
+// such store, and in nt_epilogue_store_lean hipcc put a v_cndmask rewriting the first data register directly behind the GELU-output store
+// -- every second lane group stored a zero dword in about 0.15 % of the activations of the lean 256 x 256 launches (found against float64
+// by tests/test_bench_launches_gpu.py; gone with one wait state there).  With soffset 0 the recognizer treats every such store as
+// hazardous and inserts the wait wherever a VALU write of its data follows, in every kernel these epilogues are inlined into.
+template <int AUX>
+__device__ __forceinline__ void store_b128(u32x4_t v, __amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
+    __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)(voff + soff), 0, AUX);
+}
+
 // Lean store epilogue (LEAN kernels, operands by EpiOperands::fetch_fast): bf16, every tile whole, dense rows, no bias / GELU /
 // row map.  Same values, same summation order as the general path below (results and partial sums are bit-identical); what is gone
 // is the per-row 64-bit index arithmetic, the per-row bounds checks and the layout cases: one buffer descriptor, one lane offset, a
@@ -483,7 +495,7 @@ __device__ __forceinline__ void nt_epilogue_store_fast(const char* mine, int P, 
     const __amdgpu_buffer_rsrc_t ro = make_rsrc(out, (uint32_t)M * (uint32_t)Nout * (uint32_t)sizeof(T));
     const char* src = mine + rsub * P + chunk * 16;
     auto put = [&](int it, const Vec16<T>& v) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v.v), ro, ops.voff, it * ops.vstep, 2 /* nt */);
+        store_b128<2 /* nt */>(__builtin_bit_cast(u32x4_t, v.v), ro, ops.voff, it * ops.vstep);
     };
     if (stats && br.y) {
         // BatchNorm-backward partials { sum d, sum d * (y - mean) * invstd }, d = the stored gradient behind the ReLU mask, on the
@@ -650,7 +662,7 @@ __device__ __forceinline__ void nt_epilogue_store_lean(const char* mine, int P, 
                     v.set(e, v.get(e) * gelu_slope<T>(yv[j].get(e)));
                 }
             }
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v.v), ro, voff, it * vstep, 2 /* nt */);
+            store_b128<2 /* nt */>(__builtin_bit_cast(u32x4_t, v.v), ro, voff, it * vstep);
             if (has_act) {
                 Vec16<T> ga;
 #pragma unroll
@@ -658,7 +670,7 @@ __device__ __forceinline__ void nt_epilogue_store_lean(const char* mine, int P, 
                     ga.set(e, gelu_value<T>(v.get(e)));
                 }
                 const __amdgpu_buffer_rsrc_t ra = make_rsrc(br.act, bytes);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, ga.v), ra, voff, it * vstep, 0);
+                store_b128<0>(__builtin_bit_cast(u32x4_t, ga.v), ra, voff, it * vstep);
             }
             if (rewrite) *reinterpret_cast<Vec16<T>*>(src + it * RPI * P) = v;
         }

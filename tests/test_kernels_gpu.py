@@ -322,14 +322,27 @@ def test_linear_fwd_fused_bias_gelu_stats(dtype, mnk):
     np.testing.assert_allclose(plain.float().cpu().numpy(), (a @ w.t()).numpy(), **t)
 
 
-@pytest.mark.parametrize("mnk", [(1024, 256, 256), (2560, 768, 256), (512, 2048, 512), (768, 512, 2048)])
+def _assert_256_row_tile(m, n, k):
+    """the automatic dispatch runs this launch on the 256 x 256 tile (nt_pick_tile: bf16, n % 256 == 0, m >= 16 384): one BatchNorm-partial
+    row per 256 output rows"""
+    from frhip._abi import lib
+    assert n % 256 == 0 and m >= 256 * 64
+    assert lib().frhip_conv_stat_rows(0, m, n, 1, 1, k, 1, 1, 1, 0) == (m + 255) // 256, (m, n, k)
+
+
+@pytest.mark.parametrize("mnk", [(1024, 256, 256), (2560, 768, 256), (512, 2048, 512), (768, 512, 2048),
+                                 (100352, 1024, 256), (25088, 2048, 512), (36864, 768, 256), (100352, 256, 256)])
 def test_linear_lean_epilogue_is_bit_identical_to_the_general_one(mnk):
-    """Linears made of whole 256 x 256 tiles (every Swin34 / AlterNet linear at B = 512) run the lean store epilogue (nt_epilogue_store_lean;
-    frhip_set_epi_lean): out, the GELU output and the GELU data-gradient must be the bits of the general epilogue, the per-tile sums
-    (BatchNorm partials, bias-gradient column sums: matrix pipe against VALU) agree to fp32 summation order."""
+    """Linears made of whole 256 x 256 tiles run the lean store epilogue (nt_epilogue_store_lean; frhip_set_epi_lean) once the automatic
+    dispatch picks that tile, i.e. from M = 16 384 rows: every Swin34 linear at B = 512 (M = 100 352 at 14 x 14, 25 088 at 7 x 7) and AlterNet50's
+    at B = 256 (M = 36 864 at 12 x 12).  Below that size both settings run the 128 x 128 tile, so the small shapes only hold the hook to a
+    no-op.  Out, the GELU output and the GELU data-gradient must be the bits of the general epilogue, the per-tile sums (BatchNorm partials,
+    bias-gradient column sums: matrix pipe against VALU) agree to fp32 summation order."""
     ops = _ops()
     from frhip._abi import lib
     m, n, k = mnk
+    if m >= 256 * 64:
+        _assert_256_row_tile(m, n, k)
     dt = torch.bfloat16
     a = rnd(90, (m, k)).to(dt).cuda()
     w = (rnd(91, (n, k)) * 0.2).to(dt).cuda()
@@ -352,14 +365,19 @@ def test_linear_lean_epilogue_is_bit_identical_to_the_general_one(mnk):
     np.testing.assert_allclose(l[6].cpu().numpy(), g[6].cpu().numpy(), rtol=1e-5, atol=1e-5 * float(g[6].abs().max()))
 
 
-@pytest.mark.parametrize("mkc", [(1024, 1024, 256), (2560, 256, 256), (512, 2048, 512)])
+@pytest.mark.parametrize("mkc", [(1024, 1024, 256), (2560, 256, 256), (512, 2048, 512),
+                                 (100352, 1024, 256), (100352, 768, 256), (25088, 1536, 512), (36864, 768, 256)])
 def test_linear_dgrad_with_bn_partials_lean_against_general(mkc):
     """A linear's data-gradient whose result (+ residual) is the upstream gradient of a BatchNorm (nets/SwinV2.py: x + norm(f(x)); the 1 x 1
-    form of frhip_conv_dgrad_bnred) on whole 256 x 256 tiles: the lean kernel stages its tile in two 64-row halves and forms the partials
-    { sum d, sum d xhat } on the matrix pipe -- dx bit-identical to the general epilogue, the sums to fp32 summation order."""
+    form of frhip_conv_dgrad_bnred) on whole 256 x 256 tiles -- which the automatic dispatch picks from M = 16 384 rows (Swin34's fc1 / qkv
+    data-gradients at B = 512, AlterNet50's qkv data-gradient at B = 256; the small shapes run the 128 x 128 tile either way): the lean kernel
+    stages its tile in two 64-row halves and forms the partials { sum d, sum d xhat } on the matrix pipe -- dx bit-identical to the general
+    epilogue, the sums to fp32 summation order."""
     ops = _ops()
     from frhip._abi import lib
     m, k, c = mkc
+    if m >= 256 * 64:
+        _assert_256_row_tile(m, c, k)
     dt = torch.bfloat16
     dy = rnd(95, (m, 1, 1, k)).to(dt).cuda()
     wt = (rnd(96, (c, 1, 1, k)) * 0.1).to(dt).cuda()
@@ -707,7 +725,9 @@ def test_bf16_gelu_pair_stays_within_two_to_the_minus_ten_of_the_exact_erf_form(
 
 
 @pytest.mark.parametrize("case", [("bf16 3x3 whole tiles", torch.bfloat16, 32, 12, 256, 256, 3), ("fp32 3x3 ragged", torch.float32, 6, 6, 64, 64, 3),
-                                  ("bf16 1x1 qkv data-gradient", torch.bfloat16, 32, 12, 256, 768, 1), ("bf16 1x1 small maps", torch.bfloat16, 64, 6, 512, 1536, 1)])
+                                  ("bf16 1x1 qkv data-gradient", torch.bfloat16, 32, 12, 256, 768, 1), ("bf16 1x1 small maps", torch.bfloat16, 64, 6, 512, 1536, 1),
+                                  ("bf16 1x1 AlterNet50 qkv data-gradient at B = 256", torch.bfloat16, 256, 12, 256, 768, 1),
+                                  ("bf16 1x1 AlterNet50 layer2 qkv data-gradient at B = 256", torch.bfloat16, 256, 24, 128, 384, 1)])
 def test_dgrad_carries_batchnorm_backward_sums_under_stochastic_depth(case):
     """frhip_conv_dgrad_fused_rs: the data-gradient whose result enters a BatchNorm under stochastic depth (AlterNet attention blocks:
     x + drop_path(norm(f(x))), /root/reference/nets/AlterNet_SwinV2_FAN.py:407-450) emits that BatchNorm's backward sums with the per-sample
@@ -727,6 +747,9 @@ def test_dgrad_carries_batchnorm_backward_sums_under_stochastic_depth(case):
     gen = torch.Generator().manual_seed(65)
     keep = ((torch.rand(n, generator=gen) < 0.6).float() / kp).cuda()          # 40 % dropped: both kinds of row in most tiles
     dx, part = ops.conv_dgrad(dy, wt, (n, hw, hw, c), r, r, 1, pad, residual=res, bnred=(y, st, False, keep, hw * hw, 1.0 / kp))
+    if r == 1 and dtype == torch.bfloat16 and c % 256 == 0 and rows >= 256 * 64:
+        _assert_256_row_tile(rows, c, k)            # the lean two-half BatchNorm-backward epilogue of the 256 x 256 tile
+        assert part.shape[0] == (rows + 255) // 256
     plain = ops.conv_dgrad(dy, wt, (n, hw, hw, c), r, r, 1, pad, residual=res)
     assert torch.equal(dx, plain)
     nb = lib().frhip_colreduce_blocks(rows, c, ops.dt_of(y))

@@ -14,6 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from poison import PATTERNS, PATTERN_IDS, assert_poison_applies, poisoned_empty, reset_frhip_caches
+from ref64 import ref_conv, ref_dgrad, ref_wgrad
 
 pytestmark = pytest.mark.gpu
 
@@ -73,46 +74,6 @@ def poisoned_parity(call, dtypes=(torch.float32, torch.bfloat16)):
     finally:
         reset_frhip_caches()                # no poisoned workspace survives into the next test
     return clean
-
-
-# ----------------------------------------------------------------------------------------------- float64 references (GPU, chunked)
-def ref_conv(x, w, stride, pad, chunk=16):
-    """x [N,H,W,C], w [K,R,S,C] -> float64 y [N,Ho,Wo,K] (unfold + GEMM over image chunks: no library convolution involved)"""
-    n, h, wd, c = x.shape
-    k, r, s, _ = w.shape
-    ho, wo = (h + 2 * pad - r) // stride + 1, (wd + 2 * pad - s) // stride + 1
-    wm = w.double().permute(0, 3, 1, 2).reshape(k, c * r * s)
-    out = torch.empty((n, ho, wo, k), dtype=torch.float64, device=x.device)
-    for i in range(0, n, chunk):
-        xc = x[i:i + chunk].double().permute(0, 3, 1, 2)
-        cols = F.unfold(xc, (r, s), padding=pad, stride=stride)                   # [b, C*R*S, L]
-        out[i:i + chunk] = (wm @ cols).view(xc.shape[0], k, ho, wo).permute(0, 2, 3, 1)
-    return out
-
-
-def ref_dgrad(dy, w, x_shape, stride, pad, chunk=16):
-    n, h, wd, c = x_shape
-    k, r, s, _ = w.shape
-    wm = w.double().permute(0, 3, 1, 2).reshape(k, c * r * s)
-    out = torch.empty((n, h, wd, c), dtype=torch.float64, device=dy.device)
-    for i in range(0, n, chunk):
-        d = dy[i:i + chunk].double()
-        b, ho, wo, _ = d.shape
-        cols = wm.t() @ d.reshape(b, ho * wo, k).transpose(1, 2)                  # [b, C*R*S, L]
-        out[i:i + chunk] = F.fold(cols, (h, wd), (r, s), padding=pad, stride=stride).permute(0, 2, 3, 1)
-    return out
-
-
-def ref_wgrad(dy, x, r, s, stride, pad, chunk=16):
-    n, h, wd, c = x.shape
-    k = dy.shape[3]
-    acc = torch.zeros((k, c * r * s), dtype=torch.float64, device=x.device)
-    for i in range(0, n, chunk):
-        xc = x[i:i + chunk].double().permute(0, 3, 1, 2)
-        cols = F.unfold(xc, (r, s), padding=pad, stride=stride)
-        d = dy[i:i + chunk].double()
-        acc += torch.einsum("blk,bcl->kc", d.reshape(d.shape[0], -1, k), cols)
-    return acc.view(k, c, r, s).permute(0, 2, 3, 1)                                # [K,R,S,C]
 
 
 def close(got, ref, dtype, scale=None):
