@@ -193,8 +193,23 @@ __global__ void bn_eval_kernel(int C, const float* __restrict__ gamma, const flo
     scale[c] = sc; shift[c] = beta[c] - rm[c] * sc;
 }
 
+// Eval-mode state for a pass that is differentiated: scale/shift as bn_eval_kernel plus mean = running_mean and
+// invstd = rsqrt(running_var + eps), from which the backward reductions form xhat.
+__global__ void bn_eval_state_kernel(int C, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                     const float* __restrict__ rm, const float* __restrict__ rv, float eps,
+                                     float* __restrict__ mean, float* __restrict__ invstd,
+                                     float* __restrict__ scale, float* __restrict__ shift) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const float is = rsqrtf(rv[c] + eps), sc = gamma[c] * is;
+    mean[c] = rm[c]; invstd[c] = is;
+    scale[c] = sc; shift[c] = beta[c] - rm[c] * sc;
+}
+
 // Finalise backward sums: dgamma, dbeta and the per-channel affine of  dy = ca*d_eff + cb*y + cc.
-template <bool SMALL>
+// EVAL: the BatchNorm normalised with its running statistics (eval mode), which do not depend on the batch: dy = gamma*invstd * d_eff,
+// i.e. ca = gamma*invstd, cb = cc = 0; dgamma / dbeta are the same sums.  dgamma / dbeta may be NULL (input-gradient-only backward).
+template <bool SMALL, bool EVAL = false>
 __global__ __launch_bounds__(SMALL ? 256 : 1024) void bn_bwd_finalize_kernel(const float* __restrict__ parts, int nparts, int C, float count,
                                        const float* __restrict__ gamma, const float* __restrict__ mean,
                                        const float* __restrict__ invstd, float* __restrict__ dgamma,
@@ -211,8 +226,14 @@ __global__ __launch_bounds__(SMALL ? 256 : 1024) void bn_bwd_finalize_kernel(con
         sum_parts(parts, nparts, C, c, pl, red, s1, s2);
     }
     if (pl != 0 || c >= C) return;
-    dgamma[c] += s2; dbeta[c] += s1;                 // accumulate into (caller-zeroed) .grad
-    const float gi = gamma[c] * invstd[c], m2 = s2 / count, m1 = s1 / count;
+    if (dgamma) dgamma[c] += s2;                      // accumulate into (caller-zeroed) .grad
+    if (dbeta) dbeta[c] += s1;
+    const float gi = gamma[c] * invstd[c];
+    if constexpr (EVAL) {
+        ca[c] = gi; cb[c] = 0.f; cc[c] = 0.f;
+        return;
+    }
+    const float m2 = s2 / count, m1 = s1 / count;
     ca[c] = gi; cb[c] = -gi * invstd[c] * m2; cc[c] = gi * (mean[c] * invstd[c] * m2 - m1);
 }
 
@@ -492,6 +513,30 @@ extern "C" int frhip_bn_standin_state(int c, const float* gamma, const float* be
     if (c <= 0 || !gamma || !beta || !mean || !invstd || !scale || !shift) { frhip::set_error("frhip_bn_standin_state: bad arguments"); return FRHIP_EINVAL; }
     hipLaunchKernelGGL(bn_standin_kernel, dim3((c + 63) / 64), dim3(64), 0, stream, c, gamma, beta, k, mean, invstd, scale, shift);
     return check_launch("frhip_bn_standin_state");
+}
+
+extern "C" int frhip_bn_eval_state(int c, const float* gamma, const float* beta, const float* running_mean,
+                                   const float* running_var, float eps, float* mean, float* invstd, float* scale, float* shift,
+                                   hipStream_t stream) {
+    if (c <= 0 || !gamma || !beta || !running_mean || !running_var || !mean || !invstd || !scale || !shift) {
+        set_error("frhip_bn_eval_state: bad arguments"); return FRHIP_EINVAL;
+    }
+    hipLaunchKernelGGL(bn_eval_state_kernel, dim3((c + 63) / 64), dim3(64), 0, stream, c, gamma, beta, running_mean, running_var, eps,
+                       mean, invstd, scale, shift);
+    return check_launch("frhip_bn_eval_state");
+}
+
+extern "C" int frhip_bn_bwd_finalize_eval(const float* partial, int nparts, float* scratch, int c, float count,
+                                          const float* gamma, const float* mean, const float* invstd, float* dgamma,
+                                          float* dbeta, float* ca, float* cb, float* cc, hipStream_t stream) {
+    const float* p = fold_partials(partial, nparts, c, scratch, stream);
+    if (fin_small(nparts))
+        hipLaunchKernelGGL((bn_bwd_finalize_kernel<true, true>), dim3((c + 15) / 16), dim3(256), 0, stream, p, nparts, c, count, gamma,
+                           mean, invstd, dgamma, dbeta, ca, cb, cc);
+    else
+        hipLaunchKernelGGL((bn_bwd_finalize_kernel<false, true>), dim3((c + 63) / 64), dim3(fin_threads(nparts)), 0, stream, p, nparts, c,
+                           count, gamma, mean, invstd, dgamma, dbeta, ca, cb, cc);
+    return check_launch("frhip_bn_bwd_finalize_eval");
 }
 
 extern "C" int frhip_bn_bwd_finalize(const float* partial, int nparts, float* scratch, int c, float count,

@@ -724,6 +724,244 @@ static int sf_tiles(int b, int h, int w) {
     return b * ((hp + SF_PH - 1) / SF_PH) * ((wp + SF_PW - 1) / SF_PW);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Image gradient of the stride-1 stem (the input gradient of conv3x3 -> BN -> ReLU -> MaxPool(3,2,1)), in gather form: every
+// input pixel is written once by one thread, no atomics, fixed summation order (run-to-run identical).  dy0 = ca*d + cb*y + cc is
+// the stem's BatchNorm backward (d: the pooled gradient routed to its arg-max pixel, masked by the ReLU), and dx = conv^T(dy0).
+// One workgroup = one DX_T x DX_T tile of input pixels [h0, h0+DX_T) x [w0, w0+DX_T) of one image:
+//   1. stage the pooled gradients of the DX_P x DX_P windows that can reach the tile's 1-pixel halo, zeroed where pooled <= 0 (the
+//      window's arg-max activation is the ReLU output, so pooled > 0 IS the ReLU mask there), their arg-max bytes, the weights as
+//      fp32 [tap][k][c] and, RECOMP, the input window of the conv recompute
+//   2. E[o][k] = dy0 over the DX_E x DX_E halo pixels o inside the image (0 outside), in T: a pixel receives from at most one
+//      window per row / column candidate ({h>>1, (h+1)>>1} x {w>>1, (w+1)>>1}); RECOMP recomputes y = conv(x) on the matrix pipe
+//      (StemConv, the forward kernel's instruction sequence).  Eval mode has cb = cc = 0: no recompute, no input read.
+//   3. dx[c][i] = sum_{tap, k} W[k][c][tap] * E[i - tap + 1][k]: one pixel per thread, fp32 FMAs, weights broadcast from LDS
+constexpr int DX_T = 16;
+constexpr int DX_E = DX_T + 2;                 // halo pixels per side
+constexpr int DX_P = DX_T / 2 + 2;             // pooled windows per side that reach the halo
+template <typename T> constexpr int dx_lds_bytes(bool recomp) {
+    return DX_E * DX_E * (64 * (int)sizeof(T) + 16) + DX_P * DX_P * (64 * (int)sizeof(T) + 16) + DX_P * DX_P * 80 + 9 * 64 * 16 +
+           3 * 64 * 4 + (recomp ? 3 * (DX_E + 2) * (DX_E + 2) * (int)sizeof(T) : 0);
+}
+static_assert(dx_lds_bytes<float>(true) <= 160 * 1024, "LDS budget of stem_dx_kernel");
+
+template <typename T, bool RECOMP>
+__global__ __launch_bounds__(256) void stem_dx_kernel(const float* __restrict__ x, const T* __restrict__ wp,
+                                                      const T* __restrict__ dpool, const uint8_t* __restrict__ argmax,
+                                                      const T* __restrict__ pooled, const float* __restrict__ ca,
+                                                      const float* __restrict__ cb, const float* __restrict__ cc,
+                                                      float* __restrict__ dx, int B, int H, int W) {
+    constexpr int EPV = 16 / (int)sizeof(T);
+    constexpr int ROW = 64 * (int)sizeof(T) + 16;             // bytes per pixel of the E and pooled-gradient tiles (+16: bank spread)
+    constexpr int AROW = 64 + 16;
+    constexpr int VPT = 64 / EPV;                             // 16-byte vectors per pixel
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* s_e = smem;                                                         // [DX_E * DX_E][ROW]
+    char* s_dp = s_e + DX_E * DX_E * ROW;                                     // [DX_P * DX_P][ROW]
+    uint8_t* s_arg = reinterpret_cast<uint8_t*>(s_dp + DX_P * DX_P * ROW);    // [DX_P * DX_P][AROW]
+    f32x4_t* s_w = reinterpret_cast<f32x4_t*>(s_arg + DX_P * DX_P * AROW);    // [9][64] = {W[k][0..2][tap], 0}
+    float* s_c = reinterpret_cast<float*>(s_w + 9 * 64);                      // ca, cb, cc [3][64]
+    T* xs = reinterpret_cast<T*>(s_c + 3 * 64);                               // RECOMP: [3][DX_E + 2][DX_E + 2]
+    const int lane = lane_id(), wave = wave_id(), i = lane & 15, g = lane >> 4;
+    const int Hp = (H - 1) / 2 + 1, Wp = (W - 1) / 2 + 1;
+    const int th = (H + DX_T - 1) / DX_T, tw = (W + DX_T - 1) / DX_T;
+    int tile = blockIdx.x;
+    const int n = tile / (th * tw); tile -= n * th * tw;
+    const int h0 = (tile / tw) * DX_T, w0 = (tile % tw) * DX_T;
+    const int ph0 = h0 / 2 - 1, pw0 = w0 / 2 - 1;              // first staged window
+    StemConv<T> sc;
+    if constexpr (RECOMP) {
+        sc.init(wp, xs, DX_E + 2, DX_E + 2);
+        sc.stage(xs, x + (size_t)n * 3 * H * W, h0 - 2, w0 - 2, H, W);
+    }
+    for (int v = threadIdx.x; v < 9 * 64; v += 256) {
+        const int tap = v >> 6, k = v & 63;
+        const T* wr = wp + k * 32 + tap * 3;
+        s_w[v] = f32x4_t{(float)wr[0], (float)wr[1], (float)wr[2], 0.f};
+    }
+    for (int v = threadIdx.x; v < 64; v += 256) {
+        s_c[v] = ca[v];
+        if (RECOMP) { s_c[64 + v] = cb[v]; s_c[128 + v] = cc[v]; }
+    }
+    for (int v = threadIdx.x; v < DX_P * DX_P * VPT; v += 256) {
+        const int pix = v / VPT, part = v - pix * VPT;
+        const int ph = ph0 + pix / DX_P, pw = pw0 + pix % DX_P;
+        Vec16<T> dv;
+        dv.v = typename Mma<T>::Frag{};
+        if ((unsigned)ph < (unsigned)Hp && (unsigned)pw < (unsigned)Wp) {
+            const size_t o = (((size_t)n * Hp + ph) * Wp + pw) * 64 + part * EPV;
+            dv = *reinterpret_cast<const Vec16<T>*>(dpool + o);
+            const Vec16<T> pv = *reinterpret_cast<const Vec16<T>*>(pooled + o);
+#pragma unroll
+            for (int e = 0; e < EPV; ++e)
+                if (!(pv.get(e) > 0.f)) dv.set(e, 0.f);
+        }
+        *reinterpret_cast<Vec16<T>*>(s_dp + pix * ROW + part * 16) = dv;
+    }
+    for (int v = threadIdx.x; v < DX_P * DX_P * 4; v += 256) {
+        const int pix = v >> 2, part = v & 3;
+        const int ph = ph0 + pix / DX_P, pw = pw0 + pix % DX_P;
+        f32x4_t val = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        if ((unsigned)ph < (unsigned)Hp && (unsigned)pw < (unsigned)Wp)
+            val = *reinterpret_cast<const f32x4_t*>(argmax + (((size_t)n * Hp + ph) * Wp + pw) * 64 + part * 16);
+        *reinterpret_cast<f32x4_t*>(s_arg + pix * AROW + part * 16) = val;
+    }
+    __syncthreads();
+    // ---- 2. E = dy0 over the halo: a wave takes 16 pixels per step, lane (i, g) holds channels t*16 + 4g + r of pixel i
+    for (int it = wave; it * 16 < DX_E * DX_E; it += 4) {
+        const int hp = it * 16 + i;
+        const bool valid = hp < DX_E * DX_E;
+        const int a = valid ? hp / DX_E : 0, b = valid ? hp - a * DX_E : 0;
+        const int h = h0 - 1 + a, w = w0 - 1 + b;
+        const bool inside = valid && (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
+        f32x4_t acc[4];
+        if constexpr (RECOMP) {
+            typename StemConv<T>::Frag fb[StemConv<T>::RUNS];
+            sc.gather(a, b, valid, fb);                       // halo pixel (a, b): its top-left tap is window element (a, b)
+            sc.conv(fb, acc);
+        }
+        float d[4][4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) d[t][r] = 0.f;
+        const int plo = (h >> 1) - ph0, phi = ((h + 1) >> 1) - ph0, qlo = (w >> 1) - pw0, qhi = ((w + 1) >> 1) - pw0;
+#pragma unroll 1
+        for (int pp = 0; pp < 2; ++pp) {
+            const int pl = pp == 0 ? plo : phi;
+            const bool rowuse = inside && (pp == 0 || phi != plo);
+            const int rtap = (h - (2 * (ph0 + pl) - 1)) * 3;
+#pragma unroll
+            for (int qq = 0; qq < 2; ++qq) {
+                const int pc = qq == 0 ? qlo : qhi;
+                const bool use = rowuse && (qq == 0 || qhi != qlo);
+                const int tap = rtap + (w - (2 * (pw0 + pc) - 1));
+                const int pix = use ? pl * DX_P + pc : 0;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const int ch0 = t * 16 + 4 * g;
+                    const uint32_t a4 = *reinterpret_cast<const uint32_t*>(s_arg + pix * AROW + ch0);
+                    float dv[4];
+                    if constexpr (sizeof(T) == 2) {
+                        const bf16x4_t q = *reinterpret_cast<const bf16x4_t*>(s_dp + pix * ROW + ch0 * 2);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) dv[r] = (float)q[r];
+                    } else {
+                        const f32x4_t q = *reinterpret_cast<const f32x4_t*>(s_dp + pix * ROW + ch0 * 4);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) dv[r] = q[r];
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (use && (int)((a4 >> (8 * r)) & 0xffu) == tap) d[t][r] += dv[r];
+                }
+            }
+        }
+        if (valid) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int ch0 = t * 16 + 4 * g;
+                T ev[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float e = s_c[ch0 + r] * d[t][r];
+                    if constexpr (RECOMP) e += s_c[64 + ch0 + r] * acc[t][r] + s_c[128 + ch0 + r];
+                    ev[r] = from_f32<T>(inside ? e : 0.f);
+                }
+                if constexpr (sizeof(T) == 2) {
+                    *reinterpret_cast<bf16x4_t*>(s_e + hp * ROW + ch0 * 2) = bf16x4_t{ev[0], ev[1], ev[2], ev[3]};
+                } else {
+                    *reinterpret_cast<f32x4_t*>(s_e + hp * ROW + ch0 * 4) = f32x4_t{ev[0], ev[1], ev[2], ev[3]};
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // ---- 3. transposed conv of E: thread = input pixel (h0 + u, w0 + v)
+    const int u = threadIdx.x / DX_T, v = threadIdx.x % DX_T;
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+#pragma unroll 1
+    for (int fr = 0; fr < 3; ++fr) {
+#pragma unroll
+        for (int fs = 0; fs < 3; ++fs) {
+            const char* er = s_e + ((u - fr + 2) * DX_E + (v - fs + 2)) * ROW;
+            const f32x4_t* wr = s_w + (fr * 3 + fs) * 64;
+#pragma unroll
+            for (int kc = 0; kc < VPT; ++kc) {
+                const Vec16<T> ev = *reinterpret_cast<const Vec16<T>*>(er + kc * 16);
+#pragma unroll
+                for (int e = 0; e < EPV; ++e) {
+                    const f32x4_t wv = wr[kc * EPV + e];
+                    const float q = ev.get(e);
+                    o0 += wv[0] * q; o1 += wv[1] * q; o2 += wv[2] * q;
+                }
+            }
+        }
+    }
+    const int h = h0 + u, w = w0 + v;
+    if (h < H && w < W) {
+        const size_t o = ((size_t)n * 3 * H + h) * W + w, plane = (size_t)H * W;
+        dx[o] = o0; dx[o + plane] = o1; dx[o + 2 * plane] = o2;
+    }
+}
+
+// Image gradient of the stride-2 im2col stem (AlterNet): dx = col2im(dy0 W^T) for conv3x3 / stride 2 / pad 1, gather form.  One thread = one
+// 2 x 2 quad of input pixels (2a + i, 2b + j), which reads the conv outputs (a, b), (a, b+1), (a+1, b), (a+1, b+1): every lane takes the
+// same taps (no parity divergence, the weights are LDS broadcasts) -- 9 (pixel, tap) pairs per quad.  Fixed summation order.
+template <typename T>
+__global__ __launch_bounds__(256) void stem_dx_s2_kernel(const T* __restrict__ dy0, const T* __restrict__ wp, int kp,
+                                                         float* __restrict__ dx, int B, int H, int W) {
+    constexpr int EPV = 16 / (int)sizeof(T), VPT = 64 / EPV;
+    __shared__ f32x4_t s_w[9 * 64];
+    for (int v = threadIdx.x; v < 9 * 64; v += 256) {
+        const int tap = v >> 6, k = v & 63;
+        const T* wr = wp + (size_t)k * kp + tap * 3;
+        s_w[v] = f32x4_t{(float)wr[0], (float)wr[1], (float)wr[2], 0.f};
+    }
+    __syncthreads();
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const size_t total = (size_t)B * Ho * Wo;
+    for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < total; q += (size_t)gridDim.x * 256) {
+        const int b = (int)(q % Wo);
+        const size_t rest = q / Wo;
+        const int a = (int)(rest % Ho), n = (int)(rest / Ho);
+        const bool r1 = a + 1 < Ho, c1 = b + 1 < Wo;
+        const T* row00 = dy0 + (((size_t)n * Ho + a) * Wo + b) * 64;
+        const T* row01 = c1 ? row00 + 64 : row00;
+        const T* row10 = r1 ? row00 + (size_t)Wo * 64 : row00;
+        const T* row11 = r1 && c1 ? row10 + 64 : row00;
+        f32x4_t p00 = {0.f, 0.f, 0.f, 0.f}, p01 = p00, p10 = p00, p11 = p00;
+#pragma unroll 2
+        for (int kc = 0; kc < VPT; ++kc) {
+            const Vec16<T> v00 = *reinterpret_cast<const Vec16<T>*>(row00 + kc * EPV);
+            const Vec16<T> v01 = *reinterpret_cast<const Vec16<T>*>(row01 + kc * EPV);
+            const Vec16<T> v10 = *reinterpret_cast<const Vec16<T>*>(row10 + kc * EPV);
+            const Vec16<T> v11 = *reinterpret_cast<const Vec16<T>*>(row11 + kc * EPV);
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) {
+                const int k = kc * EPV + e;
+                const float q00 = v00.get(e), q01 = c1 ? v01.get(e) : 0.f, q10 = r1 ? v10.get(e) : 0.f, q11 = r1 && c1 ? v11.get(e) : 0.f;
+                const f32x4_t w00 = s_w[0 * 64 + k], w01 = s_w[1 * 64 + k], w02 = s_w[2 * 64 + k], w10 = s_w[3 * 64 + k], w11 = s_w[4 * 64 + k],
+                              w12 = s_w[5 * 64 + k], w20 = s_w[6 * 64 + k], w21 = s_w[7 * 64 + k], w22 = s_w[8 * 64 + k];
+                p00 += w11 * q00;                                          // (2a, 2b):     tap (1,1) of (a, b)
+                p01 += w10 * q01 + w12 * q00;                              // (2a, 2b+1):   (1,0) of (a, b+1), (1,2) of (a, b)
+                p10 += w01 * q10 + w21 * q00;                              // (2a+1, 2b):   (0,1) of (a+1, b), (2,1) of (a, b)
+                p11 += w00 * q11 + w02 * q10 + w20 * q01 + w22 * q00;      // (2a+1, 2b+1)
+            }
+        }
+        const size_t plane = (size_t)H * W, o = ((size_t)n * 3 * H + 2 * a) * W + 2 * b;
+        const bool hr = 2 * a + 1 < H, wc = 2 * b + 1 < W;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float* d = dx + o + c * plane;
+            d[0] = p00[c];
+            if (wc) d[1] = p01[c];
+            if (hr) d[W] = p10[c];
+            if (hr && wc) d[W + 1] = p11[c];
+        }
+    }
+}
+
 }  // namespace frhip
 
 using namespace frhip;
@@ -833,3 +1071,45 @@ extern "C" int frhip_stem_bwd_wgrad(int dtype, const float* x, const void* wp, c
 }
 
 extern "C" int frhip_set_stem_scatter(int enabled) { const int old = g_stem_scatter; g_stem_scatter = enabled; return old; }
+
+template <typename T, bool RECOMP>
+static int sf_dx(const float* x, const void* wp, const void* dpool, const uint8_t* argmax, const void* pooled, const float* ca,
+                 const float* cb, const float* cc, float* dx, int b, int h, int w, hipStream_t stream) {
+    constexpr int lds = dx_lds_bytes<T>(RECOMP);
+    auto kern = stem_dx_kernel<T, RECOMP>;
+    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "frhip_stem_dx")) return FRHIP_ELAUNCH;
+    const long long tiles = (long long)b * ((h + DX_T - 1) / DX_T) * ((w + DX_T - 1) / DX_T);
+    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, x, (const T*)wp, (const T*)dpool, argmax, (const T*)pooled,
+                       ca, cb, cc, dx, b, h, w);
+    return check_launch("frhip_stem_dx");
+}
+
+extern "C" int frhip_stem_dx(int dtype, const float* x, const void* wp, const void* dpool, const uint8_t* argmax, const void* pooled,
+                             const float* ca, const float* cb, const float* cc, int b, int h, int w, float* dx, hipStream_t stream) {
+    if (!sf_ok(dtype, b, h, w, "frhip_stem_dx")) return FRHIP_EINVAL;
+    const bool recomp = cb != nullptr || cc != nullptr;
+    if (!wp || !dpool || !argmax || !pooled || !ca || !dx || (recomp && (!cb || !cc || !x))) {
+        set_error("frhip_stem_dx: missing operand (cb and cc are both given, with x, or both NULL)");
+        return FRHIP_EINVAL;
+    }
+    if (dtype == FRHIP_DT_BF16)
+        return recomp ? sf_dx<bf16_t, true>(x, wp, dpool, argmax, pooled, ca, cb, cc, dx, b, h, w, stream)
+                      : sf_dx<bf16_t, false>(x, wp, dpool, argmax, pooled, ca, cb, cc, dx, b, h, w, stream);
+    return recomp ? sf_dx<float, true>(x, wp, dpool, argmax, pooled, ca, cb, cc, dx, b, h, w, stream)
+                  : sf_dx<float, false>(x, wp, dpool, argmax, pooled, ca, cb, cc, dx, b, h, w, stream);
+}
+
+extern "C" int frhip_stem_dx_s2(int dtype, const void* dy0, const void* wp, int kp, int b, int h, int w, float* dx, hipStream_t stream) {
+    if (!sf_ok(dtype, b, h, w, "frhip_stem_dx_s2")) return FRHIP_EINVAL;
+    if (!dy0 || !wp || !dx || kp < 27) { set_error("frhip_stem_dx_s2: bad arguments (kp=%d)", kp); return FRHIP_EINVAL; }
+    const long long total = (long long)b * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1);     // 2 x 2 quads
+    long long blocks = (total + 255) / 256;
+    if (blocks > 65536) blocks = 65536;                    // grid-stride beyond
+    if (dtype == FRHIP_DT_BF16)
+        hipLaunchKernelGGL(stem_dx_s2_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, stream, (const bf16_t*)dy0, (const bf16_t*)wp,
+                           kp, dx, b, h, w);
+    else
+        hipLaunchKernelGGL(stem_dx_s2_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)dy0, (const float*)wp,
+                           kp, dx, b, h, w);
+    return check_launch("frhip_stem_dx_s2");
+}

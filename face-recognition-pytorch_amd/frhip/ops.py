@@ -306,8 +306,19 @@ def colstats(x2d):
 
 
 class BNState:
-    """Per-layer fp32 vectors produced by the forward finalize and consumed by apply / backward."""
-    __slots__ = ("mean", "invstd", "scale", "shift", "count")
+    """Per-layer fp32 vectors produced by the forward finalize and consumed by apply / backward.
+    eval: normalised with the running statistics (bn_eval_state): its backward is dy = gamma * invstd * d (frhip_bn_bwd_finalize_eval)."""
+    __slots__ = ("mean", "invstd", "scale", "shift", "count", "eval")
+
+    def __init__(self):
+        self.eval = False
+
+
+def _bwd_finalize(part, scratch, c, count, gamma, st, dgamma, dbeta, coef):
+    """(ca, cb, cc) into coef [3, c] and dgamma / dbeta (None: not accumulated) from the BatchNorm-backward partial sums"""
+    fn = lib().frhip_bn_bwd_finalize_eval if st.eval else lib().frhip_bn_bwd_finalize
+    check(fn(_p(part), part.shape[0], _p(scratch), c, float(count), _p(gamma), _p(st.mean), _p(st.invstd), _p(dgamma), _p(dbeta),
+             _p(coef[0]), _p(coef[1]), _p(coef[2]), _s()), "frhip_bn_bwd_finalize_eval" if st.eval else "frhip_bn_bwd_finalize")
 
 
 def bn_standin_state(gamma, beta, k, count):
@@ -349,6 +360,20 @@ def bn_eval_affine(gamma, beta, running_mean, running_var, eps=1e-5):
     return st
 
 
+def bn_eval_state(gamma, beta, running_mean, running_var, eps=1e-5):
+    """eval-mode BatchNorm state of a pass that is differentiated: bn_eval_affine's scale / shift plus mean = running_mean and
+    invstd = rsqrt(running_var + eps) (frhip_bn_eval_state, one launch)"""
+    c = gamma.numel()
+    st = BNState()
+    buf = torch.empty((4, c), dtype=torch.float32, device=gamma.device)
+    st.mean, st.invstd, st.scale, st.shift = buf[0], buf[1], buf[2], buf[3]
+    st.count = 0.0
+    st.eval = True
+    check(lib().frhip_bn_eval_state(c, _p(gamma), _p(beta), _p(running_mean), _p(running_var), eps, _p(st.mean), _p(st.invstd),
+                                    _p(st.scale), _p(st.shift), _s()), "frhip_bn_eval_state")
+    return st
+
+
 def bn_apply(y, st, relu=False, res=None, res_st=None, out=None, rowscale=None, rows_per=0):
     """rowscale [groups] fp32 + rows_per: out = res + rowscale[row // rows_per] * (y * scale + shift) (stochastic depth)"""
     c = y.shape[-1]
@@ -367,7 +392,8 @@ def bn_apply(y, st, relu=False, res=None, res_st=None, out=None, rowscale=None, 
 
 
 def bn_backward(dout, y, st, gamma, dgamma, dbeta, relu_mask=False, out=None, scratch=None, part=None, rowscale=None, rows_per=0):
-    """dy of BN (optionally through the ReLU that follows it); accumulates dgamma/dbeta (fp32, caller-zeroed).
+    """dy of BN (optionally through the ReLU that follows it); accumulates dgamma/dbeta (fp32, caller-zeroed; None: not wanted).
+    An eval-mode state (bn_eval_state) takes the eval-mode finalize: dy = gamma * invstd * d.
     part: BN-backward partial sums already produced by conv_dgrad(bnred=...) for this (dout, y) pair.
     rowscale / rows_per: the BatchNorm's output was scaled per sample in the forward pass (bn_apply(rowscale=...)): dout is scaled
     likewise inside the reduction and the apply pass"""
@@ -381,12 +407,10 @@ def bn_backward(dout, y, st, gamma, dgamma, dbeta, relu_mask=False, out=None, sc
             part = torch.empty((nb, 2, c), dtype=torch.float32, device=dev)
             check(lib().frhip_bn_bwd_reduce_rs(dt_of(y), _p(dout), _p(y), _p(st.mean), _p(st.invstd), _p(rowscale), rows_per, rows, c,
                                                _p(part), _s()), "frhip_bn_bwd_reduce_rs")
-        nb = part.shape[0]
         coef = torch.empty((3, c), dtype=torch.float32, device=dev)
         if scratch is None:
             scratch = torch.empty((64 * 2 * c,), dtype=torch.float32, device=dev)
-        check(lib().frhip_bn_bwd_finalize(_p(part), nb, _p(scratch), c, float(rows), _p(gamma), _p(st.mean), _p(st.invstd),
-                                          _p(dgamma), _p(dbeta), _p(coef[0]), _p(coef[1]), _p(coef[2]), _s()), "frhip_bn_bwd_finalize")
+        _bwd_finalize(part, scratch, c, rows, gamma, st, dgamma, dbeta, coef)
         dy = torch.empty_like(y) if out is None else out
         check(lib().frhip_bn_bwd_apply_rs(dt_of(y), _p(dout), _p(y), _p(coef[0]), _p(coef[1]), _p(coef[2]), _p(rowscale), rows_per,
                                           _p(dy), rows, c, _s()), "frhip_bn_bwd_apply_rs")
@@ -398,13 +422,10 @@ def bn_backward(dout, y, st, gamma, dgamma, dbeta, relu_mask=False, out=None, sc
         part = torch.empty((nb, 2, c), dtype=torch.float32, device=dev)
         check(lib().frhip_bn_bwd_reduce(dt_of(y), _p(dout), _p(y), _p(st.mean), _p(st.invstd), ms, mb, rows, c, _p(part), _s()),
               "frhip_bn_bwd_reduce")
-    nb = part.shape[0]
     coef = torch.empty((3, c), dtype=torch.float32, device=dev)
     if scratch is None:
         scratch = torch.empty((64 * 2 * c,), dtype=torch.float32, device=dev)
-    check(lib().frhip_bn_bwd_finalize(_p(part), nb, _p(scratch), c, float(rows), _p(gamma), _p(st.mean), _p(st.invstd),
-                                      _p(dgamma), _p(dbeta), _p(coef[0]), _p(coef[1]), _p(coef[2]), _s()),
-          "frhip_bn_bwd_finalize")
+    _bwd_finalize(part, scratch, c, rows, gamma, st, dgamma, dbeta, coef)
     dy = torch.empty_like(y) if out is None else out
     check(lib().frhip_bn_bwd_apply(dt_of(y), _p(dout), _p(y), _p(coef[0]), _p(coef[1]), _p(coef[2]), ms, mb, _p(dy),
                                    rows, c, _s()), "frhip_bn_bwd_apply")
@@ -529,31 +550,86 @@ def stem_gram(x, dtype):
     return gram
 
 
-def stem_bwd(x, wp, dpool, arg, st, gamma, dgamma, dbeta, dw27, scratch=None, part=None, gram=None, pooled=None):
-    """backward of the stem given the gradient of the pooled map: accumulates dgamma, dbeta and dw27 [64, 27] (fp32).
-    part: [rows, 2, 64] partial sums { sum d, sum d * xhat } already reduced elsewhere (skips the recompute reduction pass).
-    gram (+ pooled, the forward's output): stem_gram(x) -- the weight gradient then comes from the algebraic form (no conv
-    recompute, no scatter) instead of the recompute kernel"""
+def stem_bwd_coef(x, wp, dpool, arg, st, gamma, dgamma, dbeta, scratch=None, part=None):
+    """the stem's BatchNorm backward: accumulates dgamma, dbeta (None: not wanted) and returns coef [3, 64] = (ca, cb, cc) of
+    dy0 = ca * d + cb * y + cc.  part: [rows, 2, 64] partial sums { sum d, sum d * xhat } already reduced elsewhere (skips the
+    recompute reduction pass)"""
     b, _, h, w = x.shape
     dev = x.device
-    nb = lib().frhip_stem_blocks(b, h, w)
     if part is None:
-        part = torch.empty((nb, 2, 64), dtype=torch.float32, device=dev)
+        part = torch.empty((lib().frhip_stem_blocks(b, h, w), 2, 64), dtype=torch.float32, device=dev)
         check(lib().frhip_stem_bwd_reduce(dt_of(wp), _p(x), _p(wp), _p(dpool), _p(arg), _p(st.mean), _p(st.invstd), _p(st.scale),
                                           _p(st.shift), b, h, w, _p(part), _s()), "frhip_stem_bwd_reduce")
     coef = torch.empty((3, 64), dtype=torch.float32, device=dev)
     if scratch is None:
         scratch = torch.empty((64 * 2 * 64,), dtype=torch.float32, device=dev)
-    check(lib().frhip_bn_bwd_finalize(_p(part), part.shape[0], _p(scratch), 64, float(b * h * w), _p(gamma), _p(st.mean), _p(st.invstd),
-                                      _p(dgamma), _p(dbeta), _p(coef[0]), _p(coef[1]), _p(coef[2]), _s()),
-          "frhip_bn_bwd_finalize")
+    _bwd_finalize(part, scratch, 64, b * h * w, gamma, st, dgamma, dbeta, coef)
+    return coef
+
+
+def stem_bwd(x, wp, dpool, arg, st, gamma, dgamma, dbeta, dw27, scratch=None, part=None, gram=None, pooled=None):
+    """backward of the stem given the gradient of the pooled map: accumulates dgamma, dbeta and dw27 [64, 27] (fp32); returns
+    coef (stem_bwd_coef).  gram (+ pooled, the forward's output): stem_gram(x) -- the weight gradient then comes from the algebraic
+    form (no conv recompute, no scatter) instead of the recompute kernel"""
+    b, _, h, w = x.shape
+    dev = x.device
+    nb = lib().frhip_stem_blocks(b, h, w)
+    coef = stem_bwd_coef(x, wp, dpool, arg, st, gamma, dgamma, dbeta, scratch, part)
     slabs = torch.empty((nb, 64, 32), dtype=torch.float32, device=dev)
     if gram is not None and pooled is not None:
         check(lib().frhip_stem_bwd_wgrad_gram(dt_of(wp), _p(x), _p(wp), _p(dpool), _p(pooled), _p(arg), _p(gram), _p(coef[0]), _p(coef[1]),
                                               _p(coef[2]), b, h, w, _p(slabs), _p(dw27), _s()), "frhip_stem_bwd_wgrad_gram")
-        return
+        return coef
     check(lib().frhip_stem_bwd_wgrad(dt_of(wp), _p(x), _p(wp), _p(dpool), _p(arg), _p(coef[0]), _p(coef[1]), _p(coef[2]),
                                      _p(st.scale), _p(st.shift), b, h, w, _p(slabs), _p(dw27), _s()), "frhip_stem_bwd_wgrad")
+    return coef
+
+
+def _need_cuda(who, **tensors):
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError("%s: %s must be a tensor on the GPU" % (who, name))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (who, name))
+
+
+def stem_dx(x, wp, dpool, arg, pooled, coef, eval_mode=False):
+    """image gradient of the stride-1 stem -> dx fp32 [B,3,H,W] (frhip_stem_dx).  x fp32 [B,3,H,W] NCHW, wp = pack_stem(w, dtype, kp=32),
+    dpool / pooled [B,Hp,Wp,64] in wp's dtype, arg uint8 [B,Hp,Wp,64] (stem_fwd), coef [3,64] fp32 = (ca, cb, cc) of stem_bwd_coef.
+    eval_mode: coef came from the eval-mode finalize (cb = cc = 0): the sparse form without the conv recompute"""
+    _need_cuda("stem_dx", x=x, wp=wp, dpool=dpool, arg=arg, pooled=pooled, coef=coef)
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32:
+        raise ValueError("stem_dx: x must be fp32 [B,3,H,W], got %s %s" % (tuple(x.shape), x.dtype))
+    b, _, h, w = x.shape
+    pshape = (b, (h - 1) // 2 + 1, (w - 1) // 2 + 1, 64)
+    if wp.dtype not in _DT or tuple(wp.shape) != (64, 1, 1, 32):
+        raise ValueError("stem_dx: wp must be pack_stem(w, dtype, kp=32) [64,1,1,32], got %s %s" % (tuple(wp.shape), wp.dtype))
+    for name, t, dt in (("dpool", dpool, wp.dtype), ("pooled", pooled, wp.dtype), ("arg", arg, torch.uint8)):
+        if tuple(t.shape) != pshape or t.dtype != dt:
+            raise ValueError("stem_dx: %s must be %s %s, got %s %s" % (name, pshape, dt, tuple(t.shape), t.dtype))
+    if tuple(coef.shape) != (3, 64) or coef.dtype != torch.float32:
+        raise ValueError("stem_dx: coef must be fp32 [3,64]")
+    dx = torch.empty((b, 3, h, w), dtype=torch.float32, device=x.device)
+    cb, cc = (None, None) if eval_mode else (coef[1], coef[2])
+    check(lib().frhip_stem_dx(dt_of(wp), _p(x), _p(wp), _p(dpool), _p(arg), _p(pooled), _p(coef[0]), _p(cb), _p(cc), b, h, w, _p(dx),
+                              _s()), "frhip_stem_dx")
+    return dx
+
+
+def stem_dx_s2(dy0, wp, h, w):
+    """image gradient of the stride-2 im2col stem: dx fp32 [B,3,h,w] = col2im(dy0 W^T) (frhip_stem_dx_s2).  dy0 [B,(h-1)/2+1,(w-1)/2+1,64]
+    (the stem BatchNorm's input gradient), wp = pack_stem(w, dtype) [64,1,1,kp] in dy0's dtype"""
+    _need_cuda("stem_dx_s2", dy0=dy0, wp=wp)
+    if dy0.dim() != 4 or dy0.dtype not in _DT:
+        raise ValueError("stem_dx_s2: dy0 must be [B,Ho,Wo,64] bf16 / fp32")
+    b = dy0.shape[0]
+    if tuple(dy0.shape) != (b, (h - 1) // 2 + 1, (w - 1) // 2 + 1, 64):
+        raise ValueError("stem_dx_s2: dy0 %s does not match a %d x %d image" % (tuple(dy0.shape), h, w))
+    if wp.dtype != dy0.dtype or wp.dim() != 4 or wp.shape[0] != 64 or wp.shape[3] < 27 or wp.shape[1] * wp.shape[2] != 1:
+        raise ValueError("stem_dx_s2: wp must be pack_stem(w, dtype) [64,1,1,kp] in dy0's dtype")
+    dx = torch.empty((b, 3, h, w), dtype=torch.float32, device=dy0.device)
+    check(lib().frhip_stem_dx_s2(dt_of(dy0), _p(dy0), _p(wp), wp.shape[3], b, h, w, _p(dx), _s()), "frhip_stem_dx_s2")
+    return dx
 
 
 # ------------------------------------------------------------------------------------------ packs

@@ -138,17 +138,11 @@ def attn_block_backward(blk, s, dout, dt, bc, part2=None, next_bn=None):
     d2 = dout.reshape(m, c)
     dpo = ops.bn_backward(d2, s.po, s.st2, blk.norm2.weight.data, G(blk.norm2.weight), G(blk.norm2.bias),
                           rowscale=s.keep, rows_per=h * w, part=part2)
+    if s.st2.eval and bc.wgrad_on:                  # eval mode: norm2 is a fixed affine map, proj.bias's gradient is not zero
+        ops.colsum_accumulate(dpo, G(at.proj.bias))
     # proj.bias only shifts the input of a training-mode BatchNorm: analytically zero gradient (nets/SwinV2.py), left at zero
     dao = ops.gemm_nt(dpo, _S._transposed(s.wproj, s.wproj_t))
-    dqkv, _, _, gsum = ops.winattn_bwd(s.qkv, dao, s.bias, s.scale, b, h, w, at.num_heads, blk.window_size,
-                                       blk.shift_size, want_colsum=True, dbias=s.dbias, dscale=s.dscale,
-                                       qv_grads=(G(at.q_bias), G(at.v_bias)))
-    if gsum is None:                                 # fp32 validation kernels: column sums by a ones-GEMM
-        gsum = torch.zeros(3 * c, dtype=torch.float32, device=dout.device)
-        _S._colsum_via_gemm(dqkv, gsum)
-    if gsum is not True:                             # bf16 MFMA kernel: already added into the two gradient accumulators
-        G(at.q_bias).add_(gsum[:c])
-        G(at.v_bias).add_(gsum[2 * c:])
+    dqkv = _S._winattn_backward(blk, s, dao, bc)
     # proj's and qkv's weight gradients in ONE hand-over to the side stream (AlterNet50 11.765 -> 11.68 ms)
     bc.on_side(lambda: (ops.gemm_tn(dpo, s.ao, G(at.proj.weight)), ops.gemm_tn(dqkv, s.x2, G(at.qkv.weight))), dpo, s.ao, dqkv, s.x2)
     part = None
@@ -157,7 +151,8 @@ def attn_block_backward(blk, s, dout, dt, bc, part2=None, next_bn=None):
                                  bnred=(next_bn[0], next_bn[1], len(next_bn) > 2 and bool(next_bn[2])) + tuple(next_bn[3:]))
     else:
         dx = _S._dgrad_add(dqkv, s.wqkv, d2, s.wqkv_t)
-    _S.position_bias_backward(blk, s, bc)
+    if bc.wgrad_on:
+        _S.position_bias_backward(blk, s, bc)
     return dx.view(b, h, w, c) if next_bn is None else (dx.view(b, h, w, c), part)
 
 
@@ -264,7 +259,7 @@ class AlterNet(nn.Module):
 
     def _backward_impl(self, sv, d_emb, params):
         dt = self.dtype
-        bc = BackwardCtx(params, d_emb.device, allreduce=getattr(self, "_frhip_allreduce", False))
+        bc = BackwardCtx(params, d_emb.device, allreduce=getattr(self, "_frhip_allreduce", False), wgrad=getattr(sv, "wgrad", True))
         dout = tail_backward(self, sv, d_emb, bc)
         layers = list(self._layers())
         part = None

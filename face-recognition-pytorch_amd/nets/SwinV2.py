@@ -305,6 +305,28 @@ def _dgrad_add(dy2d, w2d, residual2d, wt=None, bnred=None):
                           residual=residual2d.view(m, 1, 1, c)).view(m, c)
 
 
+def _winattn_backward(blk, s, dao, bc):
+    """dqkv of the window attention; with parameter gradients also the q / v bias gradients (column sums of dqkv) -- d(bias) and
+    d(scale) accumulate in the position-bias batch's arena either way"""
+    G = bc.G
+    b, h, w, c = s.shape
+    at = blk.attn
+    ws, shift = getattr(blk, "window_size", 7), getattr(blk, "shift_size", 0)
+    if not bc.wgrad_on:
+        dqkv, _, _ = ops.winattn_bwd(s.qkv, dao, s.bias, s.scale, b, h, w, at.num_heads, ws, shift, dbias=s.dbias, dscale=s.dscale)
+        return dqkv
+    dqkv, _, _, gsum = ops.winattn_bwd(s.qkv, dao, s.bias, s.scale, b, h, w, at.num_heads, ws, shift, want_colsum=True,
+                                       dbias=s.dbias, dscale=s.dscale,      # d(bias), d(scale) accumulate in the batch's arena
+                                       qv_grads=(G(at.q_bias), G(at.v_bias)))
+    if gsum is None:                                 # fp32 validation kernels: column sums by a ones-GEMM
+        gsum = torch.zeros(3 * c, dtype=torch.float32, device=dao.device)
+        _colsum_via_gemm(dqkv, gsum)
+    if gsum is not True:                             # bf16 MFMA kernel: already added into the two gradient accumulators
+        G(at.q_bias).add_(gsum[:c])
+        G(at.v_bias).add_(gsum[2 * c:])
+    return dqkv
+
+
 def swin_block_backward(blk, s, dout, dt, bc, next_bn=None, part3=None):
     """next_bn=(y, st, relu): the BatchNorm whose upstream gradient the returned dx is (norm3 of the previous block, or the
     stem's for the first block): its backward reduction rides in the last data-gradient and (dx, partial) is returned.
@@ -316,6 +338,8 @@ def swin_block_backward(blk, s, dout, dt, bc, next_bn=None, part3=None):
     d2 = dout.reshape(m, c)
     # ---- MLP branch: x2 = x1 + BN(fc2(gelu(fc1(x1))))
     dmo = ops.bn_backward(d2, s.mo, s.st3, blk.norm3.weight.data, G(blk.norm3.weight), G(blk.norm3.bias), part=part3)
+    if s.st3.eval and bc.wgrad_on:                  # eval mode: norm3 is a fixed affine map, fc2.bias's gradient is not zero
+        ops.colsum_accumulate(dmo, G(blk.mlp.fc2.bias))
     # fc2.bias (and proj.bias below) only shift the input of a training-mode BatchNorm: their gradient, the column sums of
     # that BatchNorm's input gradient, is analytically zero (sum_rows dy = gamma * invstd * (sum d - N mean(d) - mean(d xhat)
     # * sum xhat) = 0); the reference gets 1e-8-sized round-off there.  Left at the arena's zero: no reduction pass.
@@ -326,23 +350,17 @@ def swin_block_backward(blk, s, dout, dt, bc, next_bn=None, part3=None):
     # in pairs (nets.AlterNet_SwinV2_FAN.attn_block_backward: 11.79 against 12.18 ms with pairs).
     bc.on_side(lambda: ops.gemm_tn(dmo, s.act, G(blk.mlp.fc2.weight).view(c, 4 * c)), dmo, s.act)
     # [M, 4C]: fc2's data-gradient with gelu'(hid) and fc1.bias's gradient (column sums) fused into its epilogue
-    dhid, _ = ops.linear_dgrad_gelu(dmo, _transposed(s.w2, s.w2_t), s.hid, colsum_into=G(blk.mlp.fc1.bias))
+    dhid, _ = ops.linear_dgrad_gelu(dmo, _transposed(s.w2, s.w2_t), s.hid, want_colsum=bc.wgrad_on, colsum_into=G(blk.mlp.fc1.bias))
     bc.on_side(lambda: ops.gemm_tn(dhid, s.x1, G(blk.mlp.fc1.weight).view(4 * c, c)), dhid, s.x1)
     # dx1 is the upstream gradient of norm2: its backward reduction over (dx1, po) rides in this data-gradient's epilogue
     dx1, part2 = _dgrad_add(dhid, s.w1, d2, s.w1_t, bnred=(s.po, s.st2, False))
     # ---- attention branch: x1 = x + BN(proj(attn(qkv(x))))
     dpo = ops.bn_backward(dx1, s.po, s.st2, blk.norm2.weight.data, G(blk.norm2.weight), G(blk.norm2.bias), part=part2)
+    if s.st2.eval and bc.wgrad_on:
+        ops.colsum_accumulate(dpo, G(at.proj.bias))
     bc.on_side(lambda: ops.gemm_tn(dpo, s.ao, G(at.proj.weight)), dpo, s.ao)
     dao = ops.gemm_nt(dpo, _transposed(s.wproj, s.wproj_t))
-    dqkv, _, _, gsum = ops.winattn_bwd(s.qkv, dao, s.bias, s.scale, b, h, w, at.num_heads, want_colsum=True,
-                                       dbias=s.dbias, dscale=s.dscale,      # d(bias), d(scale) accumulate in the batch's arena
-                                       qv_grads=(G(at.q_bias), G(at.v_bias)))
-    if gsum is None:                                 # fp32 validation kernels: column sums by a ones-GEMM
-        gsum = torch.zeros(3 * c, dtype=torch.float32, device=dout.device)
-        _colsum_via_gemm(dqkv, gsum)
-    if gsum is not True:                             # bf16 MFMA kernel: already added into the two gradient accumulators
-        G(at.q_bias).add_(gsum[:c])
-        G(at.v_bias).add_(gsum[2 * c:])
+    dqkv = _winattn_backward(blk, s, dao, bc)
     bc.on_side(lambda: ops.gemm_tn(dqkv, s.x2, G(at.qkv.weight)), dqkv, s.x2)
     part = None
     if next_bn is not None:
@@ -350,7 +368,8 @@ def swin_block_backward(blk, s, dout, dt, bc, next_bn=None, part3=None):
     else:
         dx = _dgrad_add(dqkv, s.wqkv, dx1, s.wqkv_t)
     # ---- the 169-entry position-bias MLP and the logit scale: one batched kernel launch at the end of the backward pass
-    position_bias_backward(blk, s, bc)
+    if bc.wgrad_on:
+        position_bias_backward(blk, s, bc)
     return dx.view(b, h, w, c) if next_bn is None else (dx.view(b, h, w, c), part)
 
 
@@ -426,7 +445,7 @@ class Swin(nn.Module):
 
     def _backward_impl(self, sv, d_emb, params):
         dt = self.dtype
-        bc = BackwardCtx(params, d_emb.device, allreduce=getattr(self, "_frhip_allreduce", False))
+        bc = BackwardCtx(params, d_emb.device, allreduce=getattr(self, "_frhip_allreduce", False), wgrad=getattr(sv, "wgrad", True))
         dout = tail_backward(self, sv, d_emb, bc)
         layers = list(self._layers())
         part = None

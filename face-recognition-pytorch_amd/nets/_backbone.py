@@ -110,6 +110,8 @@ def grad_like(p):
 
 
 def phys_grad(g):
+    if g is None:                   # input-gradient-only backward: no gradient arena
+        return None
     pg = g.permute(0, 2, 3, 1)
     assert pg.is_contiguous()
     return pg
@@ -227,23 +229,32 @@ class BackwardCtx:
 
     MIN_BYTES = 32 << 20
 
-    def __init__(self, params, device, allreduce=False):
+    def __init__(self, params, device, allreduce=False, wgrad=True):
+        """wgrad=False: backward for the input gradient alone (no parameter requires one) -- no arena (G(p) is None), no weight
+        gradients, no side stream, no all-reduce"""
         pre = _PREBUILT_ARENA.pop(id(params), None)
         _PREBUILT_ARENA.clear()                         # at most one live forward pass per process
-        self.grads, self.flat, self.offsets = pre if pre is not None else flat_grads(params, device)
+        self.wgrad_on = bool(wgrad)
+        if self.wgrad_on:
+            self.grads, self.flat, self.offsets = pre if pre is not None else flat_grads(params, device)
+        else:
+            self.grads, self.flat, self.offsets = {}, None, {}
         self.main = torch.cuda.current_stream()
-        self.side = side_stream(device) if _OVERLAP_WGRAD else None
+        self.side = side_stream(device) if _OVERLAP_WGRAD and self.wgrad_on else None
         self.keep = []
-        self.allreduce = bool(allreduce) and dist.is_available() and dist.is_initialized()
-        self.reduced_from = self.flat.numel()          # arena[reduced_from:] has been handed to RCCL
+        self.allreduce = self.wgrad_on and bool(allreduce) and dist.is_available() and dist.is_initialized()
+        self.reduced_from = self.flat.numel() if self.wgrad_on else 0     # arena[reduced_from:] has been handed to RCCL
         self.works = []
         self.before_join = []                          # deferred gradient work (e.g. the batched position-bias backward)
 
     def G(self, p):
-        return self.grads[p]
+        return self.grads[p] if self.wgrad_on else None
 
     def on_side(self, fn, *tensors):
-        """run fn() on the side stream after everything enqueued so far on the main stream"""
+        """run fn() (weight-gradient work) on the side stream after everything enqueued so far on the main stream; nothing when no
+        parameter gradient is wanted"""
+        if not self.wgrad_on:
+            return
         if self.side is None:
             fn()
             return
@@ -253,6 +264,8 @@ class BackwardCtx:
             fn()
 
     def wgrad(self, dy, x, gview, r, s, stride, pad):
+        if not self.wgrad_on:
+            return
         self.on_side(lambda: ops.conv_wgrad(dy, x, gview, r, s, stride, pad), dy, x, gview)
 
     def _reduce(self, lo, hi):
@@ -343,6 +356,11 @@ class DataParallel(nn.Module):
 
 # ------------------------------------------------------------------------------------------------- forward pieces
 _NBT_PENDING = None      # inside encoder_call: the num_batches_tracked counters to bump, in one multi-tensor add at the end
+# inside EncoderFn.forward: False when no parameter wants a gradient (the forward pass then prepares no weight-gradient work, e.g. the
+# stem's Gram pass); True otherwise and outside
+_FWD_WGRAD = True
+# inside an eval-mode EncoderFn.forward: the eval-mode BatchNorm states carry mean / invstd for the backward pass (bn_eval_state)
+_EVAL_GRAD = False
 
 
 def bn_forward_state(bn, part, count, training):
@@ -354,6 +372,8 @@ def bn_forward_state(bn, part, count, training):
         else:
             bn.num_batches_tracked += 1
         return st
+    if _EVAL_GRAD:
+        return ops.bn_eval_state(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, bn.eps)
     return ops.bn_eval_affine(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, bn.eps)
 
 
@@ -376,7 +396,7 @@ def stem_forward(net, x, training, sv):
         if sv is not None:
             sv.x0, sv.wp0, sv.st0, sv.arg0, sv.col, sv.p0 = x, wp0, st0, arg0, None, cur
             sv.gram = None
-            if training:
+            if training and _FWD_WGRAD:
                 # the data-only part of the stem's weight gradient (csrc/stem_algebra.hip) needs x alone: it runs on the side stream
                 # under the forward pass, and the backward pass then needs no recompute of the 112 x 112 x 64 conv map
                 side = side_stream(x.device) if _OVERLAP_WGRAD else None
@@ -397,7 +417,7 @@ def stem_forward(net, x, training, sv):
     st0 = bn_forward_state(net.bn1, part, b * h * w, training)
     cur, arg0 = ops.bn_relu_maxpool_fwd(y0, st0)
     if sv is not None:
-        sv.col, sv.y0, sv.st0, sv.arg0 = col, y0, st0, arg0
+        sv.col, sv.y0, sv.st0, sv.arg0, sv.wp0, sv.x_hw = col, y0, st0, arg0, wp0, tuple(x.shape[2:])
     return cur
 
 
@@ -419,21 +439,32 @@ def stem_reduction_operands(net, sv):
 
 
 def stem_backward(net, sv, dout, bc, part=None):
-    """part: the stem's BN-backward partial sums when the producer of dout already reduced them (stem_reduction_operands)"""
+    """part: the stem's BN-backward partial sums when the producer of dout already reduced them (stem_reduction_operands).
+    sv.want_dx: the image gradient is requested -- it is left in sv.dx (fp32 [B,3,H,W])"""
+    want_dx = getattr(sv, "want_dx", False)
     if sv.col is None:          # recompute-style stem
-        gram = getattr(sv, "gram", None)
-        if gram is not None and getattr(sv, "gram_done", None) is not None:
-            torch.cuda.current_stream().wait_event(sv.gram_done)
-            gram.record_stream(torch.cuda.current_stream())     # allocated on the side stream, read here
-        ops.stem_bwd(sv.x0, sv.wp0, dout.contiguous(), sv.arg0, sv.st0, net.bn1.weight.data, bc.G(net.bn1.weight),
-                     bc.G(net.bn1.bias), phys_grad(bc.G(net.conv1.weight)).view(64, 27), part=part, gram=gram, pooled=sv.p0)
+        dout = dout.contiguous()
+        if bc.wgrad_on:
+            gram = getattr(sv, "gram", None)
+            if gram is not None and getattr(sv, "gram_done", None) is not None:
+                torch.cuda.current_stream().wait_event(sv.gram_done)
+                gram.record_stream(torch.cuda.current_stream())     # allocated on the side stream, read here
+            coef = ops.stem_bwd(sv.x0, sv.wp0, dout, sv.arg0, sv.st0, net.bn1.weight.data, bc.G(net.bn1.weight),
+                                bc.G(net.bn1.bias), phys_grad(bc.G(net.conv1.weight)).view(64, 27), part=part, gram=gram, pooled=sv.p0)
+        else:
+            coef = ops.stem_bwd_coef(sv.x0, sv.wp0, dout, sv.arg0, sv.st0, net.bn1.weight.data, None, None, part=part)
+        if want_dx:
+            sv.dx = ops.stem_dx(sv.x0, sv.wp0, dout, sv.arg0, sv.p0, coef, eval_mode=sv.st0.eval)
         return
     da0 = ops.maxpool_bwd(dout, sv.arg0, sv.y0.shape)
     dy0 = ops.bn_backward(da0, sv.y0, sv.st0, net.bn1.weight.data, bc.G(net.bn1.weight), bc.G(net.bn1.bias), relu_mask=True)
-    m, kp = sv.col.shape
-    dwp0 = torch.zeros((64, 1, 1, kp), dtype=torch.float32, device=dout.device)
-    ops.conv_wgrad(dy0.view(m, 1, 1, 64), sv.col.view(m, 1, 1, kp), dwp0, 1, 1, 1, 0)
-    ops.unpack_stem_grad(dwp0, phys_grad(bc.G(net.conv1.weight)).view(64, 27))
+    if bc.wgrad_on:
+        m, kp = sv.col.shape
+        dwp0 = torch.zeros((64, 1, 1, kp), dtype=torch.float32, device=dout.device)
+        ops.conv_wgrad(dy0.view(m, 1, 1, 64), sv.col.view(m, 1, 1, kp), dwp0, 1, 1, 1, 0)
+        ops.unpack_stem_grad(dwp0, phys_grad(bc.G(net.conv1.weight)).view(64, 27))
+    if want_dx:
+        sv.dx = ops.stem_dx_s2(dy0, sv.wp0, *sv.x_hw)
 
 
 def prepare_conv_weights(convs, dt):
@@ -615,15 +646,18 @@ def tail_backward(net, sv, d_emb, bc):
     G = bc.G
     df = ops.bn_backward(d_emb.contiguous().float(), sv.f, sv.st3, net.bn3.weight.data, G(net.bn3.weight), G(net.bn3.bias))
     # fc.bias only shifts the input of the training-mode bn3: its gradient (the column sums of df) is analytically zero
-    # (1e-8-sized round-off in the reference) and stays at the arena's zero
+    # (1e-8-sized round-off in the reference) and stays at the arena's zero.  In eval mode bn3 is a fixed affine map: it is not.
+    if sv.st3.eval and bc.wgrad_on:
+        ops.colsum_accumulate(df, G(net.fc.bias))
     dft = ops.cast_from_f32(df, dt)
     b, kfc = sv.flat.shape
     wfct = ops.transpose2d(sv.wfc)                                  # [25088][512]
     dflat = ops.gemm_nt(dft, wfct)                                  # [B][25088]
-    dwp = torch.empty((net.emd_size, kfc), dtype=torch.float32, device=d_emb.device)
-    ops.gemm_tn(dft, sv.flat, dwp, overwrite=True)                  # 51 MB: stored once (no zero fill + atomic pass)
-    co = sv.out4.shape[3]
-    ops.fc_unpermute_grad(dwp, G(net.fc.weight), co, kfc // co)
+    if bc.wgrad_on:
+        dwp = torch.empty((net.emd_size, kfc), dtype=torch.float32, device=d_emb.device)
+        ops.gemm_tn(dft, sv.flat, dwp, overwrite=True)              # 51 MB: stored once (no zero fill + atomic pass)
+        co = sv.out4.shape[3]
+        ops.fc_unpermute_grad(dwp, G(net.fc.weight), co, kfc // co)
     dz = dflat.view(sv.out4.shape)
     if sv.dropout_mask is not None:
         dz = dz * sv.dropout_mask
@@ -637,23 +671,45 @@ class EncoderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, net, x, *params):
-        emb, sv = net._forward_impl(x, True, True)
+        global _FWD_WGRAD, _EVAL_GRAD
+        # parameter gradients are computed when any parameter wants one (a partly frozen net's other gradients are discarded);
+        # none wanted (net.requires_grad_(False), the usual adversarial-attack setup): backward for the image gradient alone
+        wgrad = any(ctx.needs_input_grad[2:])
+        training = net.training
+        _FWD_WGRAD, _EVAL_GRAD = wgrad, not training
+        try:
+            # eval mode: the unfolded forward path (the folded one, _EVAL_FOLD, keeps none of what the backward pass reads) with
+            # eval-mode BatchNorm states that carry the running statistics; dropout and stochastic depth are the identity
+            emb, sv = net._forward_impl(x, training, True)
+        finally:
+            _FWD_WGRAD, _EVAL_GRAD = True, False
+        sv.wgrad, sv.want_dx = wgrad, bool(ctx.needs_input_grad[1])
         ctx.net, ctx.sv, ctx.params = net, sv, params
         # the gradient arena of the backward pass, carved NOW: the forward pass has just been enqueued, so the host is ahead
         # of the GPU here; at the start of the backward pass (behind a short sampled head) it is not, and the ~1 ms of
         # host time the 160 views cost would be GPU idle time
         _PREBUILT_ARENA.clear()                         # at most one: a forward pass that is never differentiated leaks nothing
-        _PREBUILT_ARENA[id(params)] = flat_grads(params, x.device)
+        if wgrad:
+            _PREBUILT_ARENA[id(params)] = flat_grads(params, x.device)
         return emb
 
     @staticmethod
     def backward(ctx, d_emb):
-        grads = ctx.net._backward_impl(ctx.sv, d_emb, ctx.params)
+        sv = ctx.sv
+        grads = ctx.net._backward_impl(sv, d_emb, ctx.params)
+        dx = getattr(sv, "dx", None) if sv.want_dx else None
         ctx.sv = None
-        return (None, None) + tuple(grads.get(p) for p in ctx.params)
+        return (None, dx) + tuple(grads.get(p) for p in ctx.params)
 
 
 def encoder_call(net, x):
+    """training mode under grad mode: the autograd node (EncoderFn).  Eval mode: the autograd node when grad mode is on and x or a
+    parameter requires a gradient, else the inference path (folded BatchNorms)."""
+    differentiate = torch.is_grad_enabled() and (net.training or x.requires_grad or
+                                                 any(p.requires_grad for p in net.parameters()))
+    if differentiate and not net.training and getattr(net, "fp8", False):
+        raise NotImplementedError("frhip backbone: eval-mode differentiation of an fp8 model (frhip_fp8 / FRHIP_FP8=1) is not "
+                                  "implemented; run it under torch.no_grad(), or build the model without fp8")
     if not x.is_cuda:
         raise RuntimeError("frhip backbone: input must live on the MI355X; there is no CPU path "
                            "(the CPU restatement lives in oracle/ and is test-only)")
@@ -661,7 +717,7 @@ def encoder_call(net, x):
     global _NBT_PENDING
     _NBT_PENDING = []
     try:
-        if net.training and torch.is_grad_enabled():
+        if differentiate:
             out = EncoderFn.apply(net, x, *[p for p in net.parameters()])
         else:
             out, _ = net._forward_impl(x, net.training, False)

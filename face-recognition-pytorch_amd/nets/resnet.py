@@ -87,7 +87,7 @@ class ResNet(nn.Module):
         return emb, sv
 
     def _backward_impl(self, sv, d_emb, params):
-        bc = BackwardCtx(params, d_emb.device, allreduce=getattr(self, "_frhip_allreduce", False))
+        bc = BackwardCtx(params, d_emb.device, allreduce=getattr(self, "_frhip_allreduce", False), wgrad=getattr(sv, "wgrad", True))
         dout = tail_backward(self, sv, d_emb, bc)
         blocks = list(self._blocks())
         part = None

@@ -186,6 +186,17 @@ int frhip_bn_bwd_reduce(int dtype, const void* dout, const void* y, const float*
 int frhip_bn_bwd_finalize(const float* partial, int nparts, float* scratch, int c, float count,
                           const float* gamma, const float* mean, const float* invstd, float* dgamma,
                           float* dbeta, float* ca, float* cb, float* cc, frhip_stream_t stream);
+/* Eval-mode BatchNorm under differentiation (nn.BatchNorm2d in eval(): running statistics, no batch dependence).
+ * frhip_bn_eval_state: frhip_bn_eval_affine's scale / shift plus mean = running_mean, invstd = rsqrt(running_var + eps), the state the
+ * backward reductions (frhip_bn_bwd_reduce, the fused data-gradient epilogues, the stem's) form xhat from.
+ * frhip_bn_bwd_finalize_eval: frhip_bn_bwd_finalize for such a state -- the same dgamma += sum d*xhat, dbeta += sum d, with
+ * ca = gamma*invstd, cb = cc = 0 (dy = gamma*invstd*d).  Replaces the reference's autograd of F.batch_norm(training=False).
+ * In both finalizes dgamma / dbeta may be NULL: only (ca, cb, cc) are written (backward for the input gradient alone). */
+int frhip_bn_eval_state(int c, const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                        float* mean, float* invstd, float* scale, float* shift, frhip_stream_t stream);
+int frhip_bn_bwd_finalize_eval(const float* partial, int nparts, float* scratch, int c, float count,
+                               const float* gamma, const float* mean, const float* invstd, float* dgamma,
+                               float* dbeta, float* ca, float* cb, float* cc, frhip_stream_t stream);
 int frhip_bn_bwd_apply(int dtype, const void* dout, const void* y, const float* ca, const float* cb,
                        const float* cc, const float* mask_scale, const float* mask_shift, void* dy,
                        int rows, int c, frhip_stream_t stream);
@@ -477,6 +488,17 @@ int frhip_stem_gram(int dtype, const float* x, int b, int h, int w, float* parti
 int frhip_stem_bwd_wgrad_gram(int dtype, const float* x, const void* wp, const void* dpool, const void* pooled,
                               const uint8_t* argmax, const float* gram, const float* ca, const float* cb, const float* cc,
                               int b, int h, int w, float* slabs, float* dw, frhip_stream_t stream);
+/* Image gradient of the stem: dx [b,3,h,w] fp32 NCHW (the layout of x), every element written once, no atomics (run-to-run identical).
+ * Replaces the reference's autograd of conv1 -> bn1 -> relu -> maxpool with respect to the image (nets/resnet.py:232-235).
+ * frhip_stem_dx (stride 1, recompute-style stem): dy0 = ca*d + cb*y + cc with d = dpool routed to its arg-max pixel where pooled > 0 (the
+ *   ReLU mask), y = conv(x) recomputed (never stored); dx = conv^T(dy0).  dpool / pooled [b,hp,wp,64] `dtype`, argmax as
+ *   frhip_stem_fwd wrote it, wp = frhip_pack_stem(w, 64, 27, 32), (ca, cb, cc) from frhip_bn_bwd_finalize(_eval).  cb = cc = NULL: the
+ *   eval-mode form dy0 = ca*d (frhip_bn_bwd_finalize_eval's cb = cc = 0) -- no recompute, x may be NULL.
+ * frhip_stem_dx_s2 (stride 2, im2col stem): dx = col2im(dy0 W^T) for conv3x3 / stride 2 / pad 1; dy0 [b, (h-1)/2+1, (w-1)/2+1, 64]
+ *   `dtype` (the BatchNorm-backward output), wp = frhip_pack_stem(w, 64, 27, kp) ([64][kp] `dtype`). */
+int frhip_stem_dx(int dtype, const float* x, const void* wp, const void* dpool, const uint8_t* argmax, const void* pooled,
+                  const float* ca, const float* cb, const float* cc, int b, int h, int w, float* dx, frhip_stream_t stream);
+int frhip_stem_dx_s2(int dtype, const void* dy0, const void* wp, int kp, int b, int h, int w, float* dx, frhip_stream_t stream);
 
 /* ---- per-step operand preparation of ALL conv weights in one launch (the reference casts them implicitly under autocast,
  * nets/resnet.py:23-46 + model/FR_PartialFC.py:166-170).  Per tensor w[k][rs][c] fp32: wc[k][rs][c] (forward operand) and
