@@ -340,6 +340,142 @@ __global__ __launch_bounds__(EW_THREADS) void bn_bwd_apply_kernel(const T* __res
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Batched forms of the two passes above.  The row-at-a-time kernels compile to ONE 16-byte load in flight per lane: the compiler puts an
+// `s_waitcnt vmcnt(0)` behind every global load of the row loop (each load's conversion is scheduled in front of the next load, and the
+// counter also covers the previous row's store), and the 40 per-channel coefficients arrive as eight serialised round trips of dword loads
+// in front of the loop.  A pass with 6 - 24 waves per CU then has 6 - 24 KB in flight per CU and streams at 2 - 3 TB/s inside the step.
+// Here a thread requests the operands of U rows -- 2 U independent 16-byte loads -- before it uses the first, and fetches its coefficients
+// as 16-byte vectors in one round trip.  A block owns a contiguous run of rows_per_block rows; a row past the end of the run is loaded
+// from the run's last row (a valid address, the value is dropped) and not stored, so there is no tail loop.  The arithmetic per element
+// is the same expression as in the kernels above: outputs are bit-identical (tests/test_ew_batched_gpu.py).
+// Measured beside a resident 14 x 14 x 256 weight gradient (tools/ew_coresident.py, profiles/ew_coresident_sweep.txt): four rows in flight and
+// eight rows per thread are the best of {2, 4, 8} x {4, 8, 16} on every ResNet50 shape, e.g. 67 -> 40 us at 14 x 14 x 256.  Eight rows in flight
+// lose beside a matrix kernel (128 registers: two waves per SIMD next to a 208-register weight-gradient wave instead of three).  The budget of
+// 96 registers keeps that third wave: 208 + 3 * 96 <= 512 per lane and SIMD.
+constexpr int EW_BATCH = 4;              // rows in flight per thread
+constexpr int EW_ROWS_PER_THREAD = 8;    // rows a thread handles in all (two batches): sizes the grid
+#define EW_BATCH_REGS __attribute__((amdgpu_num_vgpr(96)))
+template <int N> __device__ __forceinline__ void coef_load(float (&dst)[N], const float* __restrict__ src) {
+#pragma unroll
+    for (int q = 0; q < N / 4; ++q) {
+        const f32x4_t v = *reinterpret_cast<const f32x4_t*>(src + 4 * q);
+        dst[4 * q] = v[0]; dst[4 * q + 1] = v[1]; dst[4 * q + 2] = v[2]; dst[4 * q + 3] = v[3];
+    }
+}
+template <int N> __device__ __forceinline__ void coef_fill(float (&dst)[N], float v) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) dst[e] = v;
+}
+
+template <typename T, bool NTL, bool RS = false, bool INPLACE = false>
+__global__ __launch_bounds__(EW_THREADS) EW_BATCH_REGS void bn_apply_batched_kernel(const T* __restrict__ y_in, const float* __restrict__ scale,
+                                                                      const float* __restrict__ shift, const T* __restrict__ res,
+                                                                      const float* __restrict__ rscale, const float* __restrict__ rshift,
+                                                                      int relu, T* __restrict__ out, int rows, int C, int rows_per_block,
+                                                                      const float* __restrict__ rowscale = nullptr, int rows_per = 1) {
+    constexpr int EPV = EW<T>::EPV, U = EW_BATCH;
+    const int vpr = C / EPV;
+    const int cg = threadIdx.x % vpr, rl = threadIdx.x / vpr, rlanes = EW_THREADS / vpr;
+    float sc[EPV], sh[EPV], rs[EPV], rb[EPV];
+    const T* y = INPLACE ? out : y_in;
+    coef_load(sc, scale + cg * EPV); coef_load(sh, shift + cg * EPV);
+    if (rscale) { coef_load(rs, rscale + cg * EPV); coef_load(rb, rshift + cg * EPV); }
+    else { coef_fill(rs, 1.f); coef_fill(rb, 0.f); }
+    const int r0 = blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
+    for (int rb0 = r0 + rl; rb0 < r1; rb0 += U * rlanes) {
+        Vec16<T> a[U], rv[U];
+        float ks[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int r = min(rb0 + u * rlanes, r1 - 1);
+            a[u] = ew_load<T, NTL>(y + (size_t)r * C + cg * EPV);
+        }
+        if (res) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int r = min(rb0 + u * rlanes, r1 - 1);
+                rv[u] = ew_load<T, NTL>(res + (size_t)r * C + cg * EPV);
+            }
+        }
+        if constexpr (RS) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) ks[u] = rowscale[min(rb0 + u * rlanes, r1 - 1) / rows_per];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if constexpr (RS) {
+#pragma unroll
+                for (int e = 0; e < EPV; ++e) {
+                    float o = (a[u].get(e) * sc[e] + sh[e]) * ks[u] + (res ? rv[u].get(e) * rs[e] + rb[e] : 0.f);
+                    a[u].set(e, relu ? fmaxf(o, 0.f) : o);
+                }
+            } else if (res) {
+#pragma unroll
+                for (int e = 0; e < EPV; ++e) {
+                    float o = a[u].get(e) * sc[e] + sh[e] + (rv[u].get(e) * rs[e] + rb[e]);
+                    a[u].set(e, relu ? fmaxf(o, 0.f) : o);
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < EPV; ++e) {
+                    float o = a[u].get(e) * sc[e] + sh[e];
+                    a[u].set(e, relu ? fmaxf(o, 0.f) : o);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int r = rb0 + u * rlanes;
+            if (r < r1) *reinterpret_cast<Vec16<T>*>(out + (size_t)r * C + cg * EPV) = a[u];
+        }
+    }
+}
+
+template <typename T, bool NTL, bool RS = false>
+__global__ __launch_bounds__(EW_THREADS) EW_BATCH_REGS void bn_bwd_apply_batched_kernel(const T* __restrict__ dout, const T* __restrict__ y,
+                                                                          const float* __restrict__ ca, const float* __restrict__ cb,
+                                                                          const float* __restrict__ cc, const float* __restrict__ mscale,
+                                                                          const float* __restrict__ mshift, T* __restrict__ dy,
+                                                                          int rows, int C, int rows_per_block,
+                                                                          const float* __restrict__ rowscale = nullptr, int rows_per = 1) {
+    constexpr int EPV = EW<T>::EPV, U = EW_BATCH;
+    const int vpr = C / EPV;
+    const int cg = threadIdx.x % vpr, rl = threadIdx.x / vpr, rlanes = EW_THREADS / vpr;
+    float a_[EPV], b_[EPV], c_[EPV], ms[EPV], mb[EPV];
+    coef_load(a_, ca + cg * EPV); coef_load(b_, cb + cg * EPV); coef_load(c_, cc + cg * EPV);
+    if (mscale) { coef_load(ms, mscale + cg * EPV); coef_load(mb, mshift + cg * EPV); }
+    else { coef_fill(ms, 0.f); coef_fill(mb, 1.f); }
+    const int r0 = blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
+    for (int rb0 = r0 + rl; rb0 < r1; rb0 += U * rlanes) {
+        Vec16<T> d[U], b[U];
+        float ks[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int r = min(rb0 + u * rlanes, r1 - 1);
+            const size_t idx = (size_t)r * C + cg * EPV;
+            d[u] = ew_load<T, NTL>(dout + idx);
+            b[u] = ew_load<T, NTL>(y + idx);
+            ks[u] = 1.f;
+            if constexpr (RS) ks[u] = rowscale[r / rows_per];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) {
+                const float yy = b[u].get(e);
+                const float de = (yy * ms[e] + mb[e] > 0.f) ? d[u].get(e) * ks[u] : 0.f;
+                b[u].set(e, a_[e] * de + b_[e] * yy + c_[e]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int r = rb0 + u * rlanes;
+            if (r < r1) *reinterpret_cast<Vec16<T>*>(dy + (size_t)r * C + cg * EPV) = b[u];
+        }
+    }
+}
+
 // out[c] += sum_p partial[p][which][c]      (block = 64 channels x 16 lanes; was one thread per channel walking all rows:
 // 199 us per call on the Swin bias gradients with ~1000 partial rows)
 __global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restrict__ partial, int nparts, int C, int which,
@@ -403,6 +539,17 @@ static int ew_row_blocks(int rows, int c, int dtype) {
     return b < 1 ? 1 : b;
 }
 
+// 1: frhip_bn_apply / frhip_bn_bwd_apply and their _rs forms run the batched kernels; 0: the row-at-a-time kernels (frhip_set_ew_batch)
+static int g_ew_batch = 1;
+
+// grid of a batched launch: every block owns rows_per_block rows = whole batches of EW_BATCH * rlanes rows
+static int ew_batched_blocks(int rows, int c, int dtype, int& rows_per_block) {
+    const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
+    rows_per_block = EW_ROWS_PER_THREAD * (EW_THREADS / (c / epv));
+    const int b = (rows + rows_per_block - 1) / rows_per_block;
+    return b < 1 ? 1 : b;
+}
+
 static bool shape_ok(int dtype, int C, const char* who) {
     const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
     if ((dtype != FRHIP_DT_BF16 && dtype != FRHIP_DT_F32) || C <= 0 || (C % epv) || (C / epv) > EW_THREADS ||
@@ -416,6 +563,12 @@ static bool shape_ok(int dtype, int C, const char* who) {
 }  // namespace frhip
 
 using namespace frhip;
+
+extern "C" int frhip_set_ew_batch(int enabled) {
+    const int old = g_ew_batch;
+    if (enabled >= 0) g_ew_batch = enabled ? 1 : 0;
+    return old;
+}
 
 extern "C" int frhip_colreduce_blocks(int rows, int c, int dtype) {
     // 0 = this (dtype, width) is not served by the element-wise kernels (the same condition shape_ok() reports with a message);
@@ -558,6 +711,17 @@ extern "C" int frhip_bn_apply_rs(int dtype, const void* y, const float* scale, c
                                  const float* rowscale, int rows_per, void* out, int rows, int c, hipStream_t stream) {
     if (!shape_ok(dtype, c, "frhip_bn_apply_rs")) return FRHIP_EINVAL;
     if (!rowscale || rows_per <= 0) { set_error("frhip_bn_apply_rs: rowscale and rows_per are required"); return FRHIP_EINVAL; }
+    if (g_ew_batch) {
+        int rpb;
+        const int blocks = ew_batched_blocks(rows, c, dtype, rpb);
+        if (dtype == FRHIP_DT_BF16)
+            hipLaunchKernelGGL((bn_apply_batched_kernel<bf16_t, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)y, scale,
+                               shift, (const bf16_t*)res, nullptr, nullptr, 0, (bf16_t*)out, rows, c, rpb, rowscale, rows_per);
+        else
+            hipLaunchKernelGGL((bn_apply_batched_kernel<float, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const float*)y, scale,
+                               shift, (const float*)res, nullptr, nullptr, 0, (float*)out, rows, c, rpb, rowscale, rows_per);
+        return check_launch("frhip_bn_apply_rs");
+    }
     const int blocks = ew_row_blocks(rows, c, dtype);
     if (dtype == FRHIP_DT_BF16)
         hipLaunchKernelGGL((bn_apply_kernel<bf16_t, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)y, scale,
@@ -586,6 +750,17 @@ extern "C" int frhip_bn_bwd_apply_rs(int dtype, const void* dout, const void* y,
                                      const float* rowscale, int rows_per, void* dy, int rows, int c, hipStream_t stream) {
     if (!shape_ok(dtype, c, "frhip_bn_bwd_apply_rs")) return FRHIP_EINVAL;
     if (!rowscale || rows_per <= 0) { set_error("frhip_bn_bwd_apply_rs: rowscale and rows_per are required"); return FRHIP_EINVAL; }
+    if (g_ew_batch) {
+        int rpb;
+        const int blocks = ew_batched_blocks(rows, c, dtype, rpb);
+        if (dtype == FRHIP_DT_BF16)
+            hipLaunchKernelGGL((bn_bwd_apply_batched_kernel<bf16_t, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)dout,
+                               (const bf16_t*)y, ca, cb, cc, nullptr, nullptr, (bf16_t*)dy, rows, c, rpb, rowscale, rows_per);
+        else
+            hipLaunchKernelGGL((bn_bwd_apply_batched_kernel<float, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const float*)dout,
+                               (const float*)y, ca, cb, cc, nullptr, nullptr, (float*)dy, rows, c, rpb, rowscale, rows_per);
+        return check_launch("frhip_bn_bwd_apply_rs");
+    }
     const int blocks = ew_row_blocks(rows, c, dtype);
     if (dtype == FRHIP_DT_BF16)
         hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)dout,
@@ -600,6 +775,23 @@ extern "C" int frhip_bn_apply(int dtype, const void* y, const float* scale, cons
                               const float* res_scale, const float* res_shift, int relu, void* out, int rows, int c,
                               hipStream_t stream) {
     if (!shape_ok(dtype, c, "frhip_bn_apply")) return FRHIP_EINVAL;
+    if (g_ew_batch) {          // same choice of loads as below: in place -> plain, through `out`; residual -> non-temporal; else plain
+        int rpb;
+        const int nblocks = ew_batched_blocks(rows, c, dtype, rpb);
+#define BN_APPLY_BATCHED(T)                                                                                                   \
+        do { if (y == out)                                                                                                    \
+            hipLaunchKernelGGL((bn_apply_batched_kernel<T, false, false, true>), dim3(nblocks), dim3(EW_THREADS), 0, stream, nullptr, \
+                               scale, shift, (const T*)res, res_scale, res_shift, relu, (T*)out, rows, c, rpb);                \
+        else if (res)                                                                                                         \
+            hipLaunchKernelGGL((bn_apply_batched_kernel<T, true>), dim3(nblocks), dim3(EW_THREADS), 0, stream, (const T*)y,   \
+                               scale, shift, (const T*)res, res_scale, res_shift, relu, (T*)out, rows, c, rpb);                \
+        else                                                                                                                  \
+            hipLaunchKernelGGL((bn_apply_batched_kernel<T, false>), dim3(nblocks), dim3(EW_THREADS), 0, stream, (const T*)y,  \
+                               scale, shift, (const T*)res, res_scale, res_shift, relu, (T*)out, rows, c, rpb); } while (0)
+        if (dtype == FRHIP_DT_BF16) BN_APPLY_BATCHED(bf16_t); else BN_APPLY_BATCHED(float);
+#undef BN_APPLY_BATCHED
+        return check_launch("frhip_bn_apply");
+    }
     const int blocks = ew_row_blocks(rows, c, dtype);
 #define BN_APPLY_GO(T, L)                                                                                                     \
     hipLaunchKernelGGL((bn_apply_kernel<T, L>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const T*)y, scale, shift,        \
@@ -625,6 +817,17 @@ extern "C" int frhip_bn_bwd_apply(int dtype, const void* dout, const void* y, co
                                   const float* cc, const float* mask_scale, const float* mask_shift, void* dy,
                                   int rows, int c, hipStream_t stream) {
     if (!shape_ok(dtype, c, "frhip_bn_bwd_apply")) return FRHIP_EINVAL;
+    if (g_ew_batch) {
+        int rpb;
+        const int nblocks = ew_batched_blocks(rows, c, dtype, rpb);
+        if (dtype == FRHIP_DT_BF16)
+            hipLaunchKernelGGL((bn_bwd_apply_batched_kernel<bf16_t, true>), dim3(nblocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)dout,
+                               (const bf16_t*)y, ca, cb, cc, mask_scale, mask_shift, (bf16_t*)dy, rows, c, rpb);
+        else
+            hipLaunchKernelGGL((bn_bwd_apply_batched_kernel<float, true>), dim3(nblocks), dim3(EW_THREADS), 0, stream, (const float*)dout,
+                               (const float*)y, ca, cb, cc, mask_scale, mask_shift, (float*)dy, rows, c, rpb);
+        return check_launch("frhip_bn_bwd_apply");
+    }
     const int blocks = ew_row_blocks(rows, c, dtype);
     if (dtype == FRHIP_DT_BF16)
         hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)dout,

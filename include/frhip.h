@@ -73,6 +73,11 @@ int frhip_set_halo_wide_dirs(int dirs);
  * (32-bit buffer-offset store epilogue, BatchNorm sums on the matrix pipe); 0 = always the general store epilogue; < 0 queries.
  * Outputs are bit-identical either way, the per-tile partial sums agree to fp32 summation order.  Returns the old value */
 int frhip_set_epi_lean(int enabled);
+/* test hook for the element-wise BatchNorm passes (frhip_bn_apply, frhip_bn_bwd_apply and their _rs forms): 1 (default) = the batched
+ * kernels (a thread requests the operands of four rows before it uses the first), 0 = the row-at-a-time kernels (one load in flight per
+ * lane), kept as the reference the batched kernels are tested against; < 0 queries.  Outputs are bit-identical either way.
+ * Returns the old value */
+int frhip_set_ew_batch(int enabled);
 /* test / micro-benchmark hook: force the NT tile (0 auto, 1 128x128, 2 256x64, 3 256x128, 4 256x256); returns the old value */
 int frhip_set_nt_tile(int tile);
 /* Inference (model/FR_PartialFC.py:205-211: encoder.eval(); nets/resnet.py:89-103 with BatchNorm in eval mode): convolution with the
