@@ -4,6 +4,7 @@
 // drop-in nets.ArcFace / nets.PartialFC.DistCrossEntropy keep the reference's tensor-in / tensor-out contract.
 // HBM-bound row kernels: one 256-thread block per row, 16-byte accesses where the row pitch allows.
 #include "common.h"
+#include "cross_pair.h"
 #include "frhip.h"
 
 namespace frhip {
@@ -206,14 +207,8 @@ __global__ void pair_score_kernel(const float* __restrict__ e1, const float* __r
     if (idx >= 0 && idx <= 100000) atomicAdd(labels[i] ? hist_genuine + idx : hist_imposter + idx, 1);
 }
 
-// ---- cross-matching per-pair arithmetic, shared by cross_score_kernel (pair list) and cross_hist_kernel (histograms only) so the
-// two cannot drift apart.  sum += (double)(float)(e[j][k] - e[i][k])^2 in ascending k: the square of a float is exact in double
-// (48 significant bits fit in 53), so a fused or a separate multiply-add give the same sum and only the order of the adds matters.
-__device__ __forceinline__ double cross_acc(double sum, float ej, float ei) {
-    const double dd = (double)(ej - ei);
-    return sum + dd * dd;
-}
-__device__ __forceinline__ double cross_pair_score(double sum) { return 1.0 - sum / 4.0; }
+// ---- cross-matching per-pair arithmetic: cross_acc / cross_pair_score (cross_pair.h) are shared by cross_score_kernel (pair
+// list), cross_hist_kernel (histograms only) and the 1:N search (gallery_topk.hip) so the routes cannot drift apart.
 // the reference's bin int(99999 * score); counted only when it lands in [0, 100000]
 __device__ __forceinline__ int cross_bin(double score) { return (int)((1e5 - 1.0) * score); }
 // threshold slot: the smallest t in [0, 100001] with score <= t / 1e5, where t / 1e5 is the correctly rounded double quotient that
@@ -254,8 +249,6 @@ __global__ __launch_bounds__(256) void cross_score_kernel(const float* __restric
 // 8 x 8 register tile of float64 sums; row slices of both blocks are staged through LDS in K-chunks of 32, [k][row] so that one
 // thread's 8 rows at one k are two ds_read_b128.  Columns k >= d are zero on both sides and add exactly 0.  No MFMA: its internal
 // order of sums is not the sequential one.
-constexpr int CH_T = 128, CH_KC = 32, CH_LD = CH_T + 4;
-
 __device__ __forceinline__ void hist_add(unsigned long long* h, int k) {
     __hip_atomic_fetch_add(h + k, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

@@ -1021,6 +1021,53 @@ def cross_hist(e, labels_i64, bounds=None):
     return hg, hi, tg, ti
 
 
+# ------------------------------------------------------------------------------------------ 1:N identification
+GALLERY_TOPK_PAIRS_PER_LAUNCH = CROSS_HIST_PAIRS_PER_LAUNCH     # same reasoning: one launch stays short on a shared device
+
+
+def gallery_topk_bands(p, g, pairs_per_launch=GALLERY_TOPK_PAIRS_PER_LAUNCH):
+    """gallery row boundaries [0, b1, ..., g] of the launches of gallery_topk: bands of about pairs_per_launch / p rows, a
+    multiple of the kernel's 128-row tile"""
+    rows = max(128, pairs_per_launch // max(p, 1) // 128 * 128)
+    return list(range(0, g, rows)) + [g]
+
+
+def gallery_topk_workspace(p, k, device):
+    """the split lists of one frhip_gallery_topk launch (frhip_gallery_topk_workspace bytes), one buffer per (device, stream)"""
+    need = ctypes.c_int64(0)
+    check(lib().frhip_gallery_topk_workspace(p, k, ctypes.byref(need)), "frhip_gallery_topk_workspace")
+    key = ("gallery_topk", torch.device(device).index, _s())
+    ws = _WORKSPACES.get(key)
+    if ws is None or ws.numel() * 8 < need.value:
+        ws = _WORKSPACES[key] = torch.empty(max(1, need.value // 8), dtype=torch.float64, device=device)
+    return ws
+
+
+def gallery_topk(probe, gallery, k, exclude=None, bounds=None):
+    """for every row of probe [P,d] fp32 the k best rows of gallery [G,d] fp32 -> (top_score float64 [P,k], top_index int64 [P,k]) on
+    the device: frhip_cross_score's scores to the bit, score descending then gallery index ascending, unfilled slots -inf / -1
+    (include/frhip.h frhip_gallery_topk).  `exclude` int64 [P]: the one gallery row probe i must not match (-1: none).  `bounds`:
+    gallery row boundaries of the launches, 0 first and G last (default gallery_topk_bands(P, G))."""
+    p, d = probe.shape
+    g = gallery.shape[0]
+    dev = probe.device
+    assert gallery.dim() == 2 and gallery.shape[1] == d, "gallery_topk: probe [P,d] and gallery [G,d] expected"
+    assert probe.dtype == torch.float32 and gallery.dtype == torch.float32, "gallery_topk: fp32 embeddings expected"
+    assert exclude is None or (exclude.dtype == torch.int64 and exclude.numel() == p), "gallery_topk: exclude is int64 [P]"
+    bounds = gallery_topk_bands(p, g) if bounds is None else list(bounds)
+    if not bounds or bounds[0] != 0 or bounds[-1] != g or any(b1 < b0 for b0, b1 in zip(bounds, bounds[1:])):
+        raise ValueError("gallery_topk: bounds %r do not cover [0, %d) in order" % (bounds[:8], g))
+    ptrs = (_p(probe), _p(gallery), _p(exclude))
+    k = int(k)
+    top_score = torch.full((p, max(k, 0)), float("-inf"), dtype=torch.float64, device=dev)
+    top_index = torch.full((p, max(k, 0)), -1, dtype=torch.int64, device=dev)
+    ws = gallery_topk_workspace(p, k, dev)
+    for g0, g1 in zip(bounds, bounds[1:]):
+        check(lib().frhip_gallery_topk(*ptrs, p, g, d, k, g0, g1, _p(top_score), _p(top_index), _p(ws), ws.numel() * 8, _s()),
+              "frhip_gallery_topk")
+    return top_score, top_index
+
+
 # ------------------------------------------------------------------------------------------ fp8 weight path (BASELINE cfg 5)
 FP8_ACT_SCALE = 1.0        # static per-tensor scale of the fp8 activation copies: post-BatchNorm activations are O(1), e4m3 reaches 448
 

@@ -226,8 +226,16 @@ class Model(nn.Module):
         roc, eer_th = ev.performance_roc(hg, hi, min_level=getattr(self.conf, "min_level", 3),
                                          max_level=getattr(self.conf, "max_level", 9))
         acc = ev.cross_accuracy(embeds, labels, eer_th) if streaming else ev.performance_acc(scores, pair_labels, eer_th)
-        return {"dataset_name": name, "acc": acc, "roc": roc, "eer_th": eer_th,
-                "infer_time": float(np.mean([o[f"{name}_infer_time"] for o in outputs]))}
+        out = {"dataset_name": name, "acc": acc, "roc": roc, "eer_th": eer_th,
+               "infer_time": float(np.mean([o[f"{name}_infer_time"] for o in outputs]))}
+        # conf.cross_test_identification = k (not in the reference): leave-one-out 1:N search of the test set against itself, the k
+        # best other images of every image; identities with a single image are the non-mated probes of the open-set figures
+        k = getattr(self.conf, "cross_test_identification", None)
+        if k:
+            top_score, top_index = ev.identify(embeds, embeds, k=int(k), exclude_self=True)
+            ranks = tuple(r for r in (1, 5, 10) if r <= int(k))
+            out["identification"] = ev.identification_rates(top_score, top_index, labels, labels, ranks=ranks, exclude_self=True)
+        return out
 
     def training_epoch_end(self, outputs, t=None):
         self.sch.step() if self.sch is not None else None

@@ -459,6 +459,22 @@ int frhip_cross_score(const float* e, const int64_t* labels, int n, int d, doubl
  * Device memory stays O(n d) at any n.  Bad arguments (n < 0, d <= 0, a band outside [0, n]) return FRHIP_EINVAL. */
 int frhip_cross_hist(const float* e, const int64_t* labels, int64_t n, int d, int64_t i0, int64_t i1, uint64_t* hist_genuine,
                      uint64_t* hist_imposter, uint64_t* thr_genuine, uint64_t* thr_imposter, frhip_stream_t stream);
+/* 1:N identification (not in the reference): for every row of probe [p][d] the k best rows of the band [g0, g1) of gallery [g][d],
+ * MERGED into the lists top_score [p][k] float64 / top_index [p][k] int64, which the caller initialises once to -inf / -1; calls
+ * over disjoint bands that cover [0, g) leave, in any order and split, the lists of one call.  The P x G scores are never written.
+ *   score : frhip_cross_score's, to the bit (float64 sum of squared float32 differences gallery - probe in ascending column,
+ *           score = 1 - sum / 4).
+ *   order : total -- score descending, then gallery index ascending; exact ties come out lowest index first.
+ *   a pair with a NaN score is never listed; unfilled slots (fewer than k candidates) hold index -1, score -inf, at the end.
+ *   exclude [p] (NULL = none): the one gallery row that probe i must not match, -1 for none (exclude[i] = i: leave-one-out).
+ *   1 <= k <= 64, 1 <= d <= 2^27 (any d, not only multiples of the K chunk).  workspace: frhip_gallery_topk_workspace(p, k, &bytes) bytes, written before it is read; it holds the
+ *   lists of the gallery splits of one launch, 2 MiB x k or one list per probe row if that is more.
+ * p = 0 or an empty band: nothing to do.  Bad arguments (negative sizes, k out of range, a band outside [0, g], null pointers
+ * with work to do, a workspace too small) return FRHIP_EINVAL. */
+int frhip_gallery_topk(const float* probe, const float* gallery, const int64_t* exclude, int64_t p, int64_t g, int d, int k,
+                       int64_t g0, int64_t g1, double* top_score, int64_t* top_index, void* workspace, size_t workspace_bytes,
+                       frhip_stream_t stream);
+int frhip_gallery_topk_workspace(int64_t p, int k, int64_t* bytes);
 
 /* ---- recompute-style stem (stride 1): conv3x3(3->64) -> BN -> ReLU -> MaxPool(3,2,1) of nets/resnet.py:232-235 without ever
  * writing the conv output map or an im2col matrix; every pass recomputes the conv from x [b,3,h,w] fp32 NCHW and
