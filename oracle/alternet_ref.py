@@ -8,8 +8,12 @@ Follows /root/reference/nets/AlterNet_SwinV2_FAN.py:
     pairs inserted by the rule of stack_layers (:685-731), tail bn2 -> ReLU -> Dropout -> AdaptiveAvgPool(6,6)
     -> fc(512*36 -> 512) -> bn3.  AlterNet50 = blocks [3,4,14,4], attention pairs [0,1,4,1], heads (2,4,8,16),
     only constructible at img_size 192.
-DropPath(0.1) and Dropout are identity in eval; training fixtures set both to zero.
+DropPath(0.1) (:372, :444) and Dropout(0.5) (:667, :745) are identity in eval.  In training the RNG-free fixtures set both to zero; the
+*_stochastic fixtures inject portable draws (oracle.recipe.keep_factors / dropout_mask): `keeps` holds one row of per-sample factors
+{0, 1/keep_prob} per attention block in network order (timm's drop_path with scale_by_keep, applied to the normalised branch), and
+`dropout_mask` is a {0, 1/(1-p)} multiplier in NCHW layout applied after the ReLU of bn2, before the pool and the flatten.
 """
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -20,7 +24,6 @@ WINDOWS = (6, 6, 6, 3)
 
 
 def coords_table(ws):
-    import numpy as np
     r = torch.arange(-(ws - 1), ws, dtype=torch.float32) / (ws - 1) * 8
     t = torch.stack(torch.meshgrid([r, r], indexing="ij")).permute(1, 2, 0).contiguous().unsqueeze(0)
     return torch.sign(t) * torch.log2(torch.abs(t) + 1.0) / np.log2(8)
@@ -118,8 +121,8 @@ def fill_special(sd, spec):
     return sd
 
 
-def attn_block(sd, p, x, heads, ws, shift, training):
-    """x NCHW -> NCHW:  x + BN(attention over (shifted) ws x ws windows)"""
+def attn_block(sd, p, x, heads, ws, shift, training, keep=None):
+    """x NCHW -> NCHW:  x + BN(attention over (shifted) ws x ws windows); keep [B]: stochastic-depth factor of every sample's branch"""
     b, c, h, w = x.shape
     y = x.permute(0, 2, 3, 1)
     if shift:
@@ -129,18 +132,61 @@ def attn_block(sd, p, x, heads, ws, shift, training):
     a = swin_ref.from_windows(a, b, h, w, ws)
     if shift:
         a = torch.roll(a, shifts=(shift, shift), dims=(1, 2))
-    return x + resnet_ref._bn(sd, p + ".norm2", a.permute(0, 3, 1, 2), training)
+    n = resnet_ref._bn(sd, p + ".norm2", a.permute(0, 3, 1, 2), training)
+    if keep is not None:
+        n = n * keep.view(-1, 1, 1, 1)
+    return x + n
 
 
-def alter_forward(sd, x, name, training, emd_size=512):
+def attn_positions(name, emd_size=512, img=192):
+    """indices into alter_plan() of the attention blocks, network order (= the rows of `keeps`)"""
+    return [i for i, e in enumerate(alter_plan(name, emd_size, img)) if e[2] == "attn"]
+
+
+def check_keep_factors(keeps, name, keep_prob, emd_size=512, img=192):
+    """the conditions a stored stochastic-depth seed must meet for a fixture to exercise the wiring: enough drops, blocks with none and
+    with several, a sample dropped in consecutive blocks, a drop in an attention block that FOLLOWS a conv block's BatchNorm consumer and
+    in one that follows another attention block (the two shapes of the reduction handed to the next layer's data-gradient in backward),
+    and no block that drops every sample (its BatchNorm gradients would vanish and pin nothing)."""
+    plan, pos = alter_plan(name, emd_size, img), attn_positions(name, emd_size, img)
+    k = keeps.numpy()
+    assert k.shape[0] == len(pos) and set(np.unique(k).tolist()) == {0.0, float(np.float32(1.0) / np.float32(keep_prob))}
+    z = k == 0
+    assert z.sum() >= 8, z.sum()
+    assert (z.sum(1) == 0).any() and (z.sum(1) >= 2).any() and not z.all(1).any()
+    runs = [j for j in range(len(pos) - 1) if pos[j + 1] == pos[j] + 1]
+    assert any((z[j] & z[j + 1]).any() for j in runs)               # one sample dropped in two attention blocks that are neighbours in the network
+    # the attention block in front of a BasicBlock / in front of another attention block (the last of each kind in network order)
+    before_basic = [j for j in range(len(pos)) if pos[j] + 1 < len(plan) and plan[pos[j] + 1][2] == "basic"]
+    before_attn = [j for j in range(len(pos)) if pos[j] + 1 < len(plan) and plan[pos[j] + 1][2] == "attn"]
+    assert z[before_basic[-1]].any() and z[before_attn[-1]].any()
+
+
+def tail(sd, y, training, dropout_mask=None, kink=0.0):
+    """bn2 -> ReLU -> [Dropout as a multiplier, NCHW] -> AdaptiveAvgPool(6,6) -> flatten -> fc -> bn3
+    kink != 0 (tools/kink_shift.py only): the ReLU's threshold moved there, values unchanged -- what an implementation whose bn2 output is
+    off by `kink` decides differently"""
+    y = resnet_ref._bn(sd, "bn2", y, training)
+    y = F.relu(y) if kink == 0.0 else y * (y > kink)
+    if dropout_mask is not None:
+        y = y * dropout_mask
+    y = F.adaptive_avg_pool2d(y, (6, 6)).reshape(y.shape[0], -1)
+    y = F.linear(y, sd["fc.weight"], sd["fc.bias"])
+    return resnet_ref._bn(sd, "bn3", y, training)
+
+
+def alter_forward(sd, x, name, training, emd_size=512, keeps=None, dropout_mask=None):
     img = x.shape[-1]
     y = F.conv2d(x, sd["conv1.weight"], None, 2, 1)
     y = F.relu(resnet_ref._bn(sd, "bn1", y, training))
     y = F.max_pool2d(y, 3, 2, 1)
+    ki = 0
     for li, idx, kind, cin, cout, stride, ds, hd, ws, shift, res in alter_plan(name, emd_size, img):
         p = "layer%d.%d" % (li, idx)
-        y = resnet_ref.basic_block(sd, p, y, stride, ds, training) if kind == "basic" else attn_block(sd, p, y, hd, ws, shift, training)
-    y = F.relu(resnet_ref._bn(sd, "bn2", y, training))
-    y = F.adaptive_avg_pool2d(y, (6, 6)).reshape(y.shape[0], -1)
-    y = F.linear(y, sd["fc.weight"], sd["fc.bias"])
-    return resnet_ref._bn(sd, "bn3", y, training)
+        if kind == "basic":
+            y = resnet_ref.basic_block(sd, p, y, stride, ds, training)
+        else:
+            y = attn_block(sd, p, y, hd, ws, shift, training, keep=None if keeps is None else keeps[ki])
+            ki += 1
+    assert keeps is None or ki == len(keeps)
+    return tail(sd, y, training, dropout_mask)

@@ -90,3 +90,16 @@ def probe(t, k=256):
     t = t.detach().double().reshape(-1)
     pos = torch.from_numpy(probe_positions(t.numel(), k))
     return torch.cat([t.sum().view(1), t.norm().view(1), t[pos]]).numpy()
+
+
+def keep_factors(seed, blocks, batch, keep_prob):
+    """stochastic-depth factors of `blocks` residual branches, one row per block in network order: float32 [blocks, batch] of
+    {0, 1/keep_prob} (timm's drop_path with scale_by_keep: a sample's branch is kept with probability keep_prob and scaled by its inverse)"""
+    kept = rng(seed).random(size=(blocks, batch)) < keep_prob
+    return torch.from_numpy(kept.astype(np.float32)) / torch.tensor(keep_prob, dtype=torch.float32)
+
+
+def dropout_mask(seed, shape_nchw, p):
+    """nn.Dropout(p) as a multiplier: float32 {0, 1/(1-p)} of the reference's NCHW shape, an element is zeroed with probability p"""
+    kept = rng(seed).random(size=tuple(shape_nchw)) >= p
+    return torch.from_numpy(kept.astype(np.float32)) / torch.tensor(1.0 - p, dtype=torch.float32)

@@ -145,7 +145,8 @@ def swin_block(sd, p, x, heads, training):
 
 
 def swin_forward(sd, x, name, training, emd_size=512, dropout_mask=None):
-    """dropout_mask: None = no dropout (eval, or the p=0 training fixtures); else a {0, 2}-valued tensor."""
+    """dropout_mask: None = no dropout (eval, or the p=0 training fixtures); else the tail's Dropout(0.5) as a {0, 2}-valued multiplier
+    of the NCHW bn2 output, before the pool and the flatten (oracle.recipe.dropout_mask; fixture swin34_b8_train_dropout)."""
     y = F.conv2d(x, sd["conv1.weight"], None, 1, 1)
     y = F.relu(resnet_ref._bn(sd, "bn1", y, training))
     y = F.max_pool2d(y, 3, 2, 1)

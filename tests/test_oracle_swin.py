@@ -82,3 +82,20 @@ def test_swin34_whole_net_training_mode(golden):
     y.backward(recipe.normal(int(g["seed"]) + 2, tuple(y.shape), 0.05))
     assert {"gprobe." + k for k in names} == {k for k in g if k.startswith("gprobe.")}
     check_whole_net_train(g, {k: sd[k].grad for k in names}, y.detach().numpy(), {k: v.detach() for k, v in sd.items()}, noise=("fc.bias", "bn2.bias"))
+
+
+def test_swin34_whole_net_training_mode_with_tail_dropout(golden):
+    """the same pass with the tail's Dropout(0.5) ON (/root/reference/nets/SwinV2.py:516, :559: bn2 -> dropout -> pool -> flatten, the
+    mask multiplies an NCHW tensor): the reference ran on a mask injected from oracle.recipe.dropout_mask, the fixture stores its seed"""
+    from wholenet import stochastic_draws
+    g = golden("swin34_b8_train_dropout")
+    _, mask = stochastic_draws(g)
+    spec = swin_ref.swin_spec("Swin34")
+    sd = swin_ref.fill_special(recipe.fill_state(spec, int(g["seed"])), spec)
+    names = [k for k, _, kind in spec if kind in ("conv", "linear_w", "linear_b", "bn_w", "bn_b", "logit_scale")]
+    for k in names:
+        sd[k].requires_grad_(True)
+    y = swin_ref.swin_forward(sd, recipe.images(int(g["seed"]) + 1, int(g["batch"])), "Swin34", True, dropout_mask=mask)
+    y.backward(recipe.normal(int(g["seed"]) + 2, tuple(y.shape), 0.05))
+    assert {"gprobe." + k for k in names} == {k for k in g if k.startswith("gprobe.")}
+    check_whole_net_train(g, {k: sd[k].grad for k in names}, y.detach().numpy(), {k: v.detach() for k, v in sd.items()}, noise=("fc.bias", "bn2.bias"))

@@ -189,6 +189,19 @@ def test_swin34_whole_net_training_mode_fp32_matches_reference_fixture(golden):
     check_whole_net_train(g, grads, out, bufs, rtol=2e-3, noise=("fc.bias", "bn2.bias"))      # measured: <= 6e-4 of the rms on every tensor
 
 
+def test_swin34_whole_net_tail_dropout_fp32_matches_reference_fixture(golden):
+    """the same network with the tail's Dropout(0.5) ON, as cfg 4 trains it (/root/reference/nets/SwinV2.py:516, :559), against the real
+    reference on the same mask (fixture swin34_b8_train_dropout): wholenet.inject_draws hands frhip.ops.dropout_mask's caller the
+    reference's NCHW mask permuted to the product's NHWC and asserts that the tail consumed it.  Settings of the RNG-free test."""
+    from wholenet import check_whole_net_train, stochastic_draws, whole_net_train_on_gpu
+    g = golden("swin34_b8_train_dropout")
+    _, mask = stochastic_draws(g)
+    net = _net("Swin34", "fp32", int(g["seed"]))
+    assert net.dropout.p == float(g["dropout_p"])
+    grads, out, bufs = whole_net_train_on_gpu(net, g, dropout_mask=mask)
+    check_whole_net_train(g, grads, out, bufs, rtol=2e-3, noise=("fc.bias", "bn2.bias"))
+
+
 def test_swin34_bf16_training_step_tracks_the_reference_fixture(golden):
     """bf16 MFMA mode on the same inputs: embeddings within 5 %, the large gradients point the reference's way"""
     from wholenet import whole_net_train_on_gpu

@@ -478,19 +478,53 @@ FULL_ALTERNET50 = ("conv1.weight", "layer1.0.conv1.weight", "layer2.2.attn.qkv.w
                    "bn3.bias")
 
 
-def _whole_net_train(name, net, spec, fill_special, seed, x, full):
-    """One training-mode forward/backward of a whole reference backbone (BatchNorm in batch-statistics mode, stochastic depth = identity
-    through the DropPath stub, tail Dropout p = 0: RNG-free), batch 8 so that the tail BatchNorm1d is well conditioned.  Stored: the
-    embeddings, a probe (sum, l2, 256 elements at portable positions) of EVERY parameter gradient, full tensors of the named ones and of
-    every attention block's first-in-stage qkv / cpb gradients that fit, probes of the running statistics."""
+class InjectedDropout(torch.nn.Module):
+    """stands in for the reference net's `dropout` (nn.Dropout(0.5)): the same multiplication, by an injected {0, 1/(1-p)} mask
+    (oracle.recipe.dropout_mask, NCHW like the tensor the reference masks) instead of a draw from torch's generator"""
+
+    def __init__(self, mask):
+        super().__init__()
+        self.mask, self.used = mask, 0
+
+    def forward(self, x):
+        if not self.training:
+            return x
+        assert x.shape == self.mask.shape
+        self.used += 1
+        return x * self.mask
+
+
+def _inject(net, keeps, dropout_mask):
+    """switch the reference net's two random paths to injected draws (None: off, as in the RNG-free fixtures)"""
+    drop_path = sys.modules["timm.models.layers"].DropPath
+    drop_path.feed = None if keeps is None else list(keeps)
+    if dropout_mask is None:
+        net.dropout.p = 0.0
+    elif isinstance(net.dropout, InjectedDropout):
+        net.dropout.mask = dropout_mask
+    else:
+        assert net.dropout.p == 0.5
+        net.dropout = InjectedDropout(dropout_mask)
+    return drop_path
+
+
+def _whole_net_train(name, net, spec, fill_special, seed, x, full, keeps=None, dropout_mask=None, **extra):
+    """One training-mode forward/backward of a whole reference backbone (BatchNorm in batch-statistics mode), batch 8 so that the tail
+    BatchNorm1d is well conditioned.  keeps / dropout_mask None: stochastic depth = identity through the DropPath stub, tail Dropout
+    p = 0 (RNG-free); else the injected draws (DropPath stub's second mode, InjectedDropout).  Stored: the embeddings, a probe (sum, l2,
+    256 elements at portable positions) of EVERY parameter gradient, full tensors of the named ones, probes of the running statistics,
+    and whatever `extra` names (the seeds of the injected draws)."""
     assert [k for k, _, _ in spec] == list(net.state_dict().keys()), name
     sd = fill_special(recipe.fill_state(spec, seed), spec)
     net.load_state_dict(sd, strict=True)
     net.train()
-    net.dropout.p = 0.0
+    drop_path = _inject(net, keeps, dropout_mask)
     y = net(x)
+    assert keeps is None or drop_path.feed == []            # every attention block took its row
+    assert dropout_mask is None or net.dropout.used == 1
+    drop_path.feed = None
     y.backward(recipe.normal(seed + 2, tuple(y.shape), 0.05))
-    arrs = dict(out=y.detach(), batch=x.shape[0], seed=seed)
+    arrs = dict(out=y.detach(), batch=x.shape[0], seed=seed, **extra)
     for k, p in net.named_parameters():
         arrs["gprobe." + k] = recipe.probe(p.grad)
         if k in full:
@@ -502,6 +536,8 @@ def _whole_net_train(name, net, spec, fill_special, seed, x, full):
         if "running" in k:
             arrs["after." + k] = recipe.probe(b.float())
     save(name, **arrs)
+    if keeps is not None or dropout_mask is not None:
+        assert os.path.getsize(os.path.join(OUT, name + ".npz")) <= (1 << 20), name
 
 
 # ----------------------------------------------------------------------------- SwinV2-style backbone
@@ -511,10 +547,25 @@ def _swin_ref():
     import torch.nn as nn
     if "timm.models.layers" not in sys.modules:
         class DropPath(nn.Module):
-            def __init__(self, p=0.0):
+            """Container stub of timm.models.layers.DropPath (timm is not installed here).  THIS PROJECT'S READING of timm's drop_path, not
+            timm itself; everything around it is the real reference code.  Two modes:
+              * DropPath.feed is None (default): the identity -- the RNG-free fixtures.
+              * DropPath.feed is a list of per-sample factor rows (oracle.recipe.keep_factors, one row per attention block in network
+                order): timm's arithmetic with scale_by_keep=True, `x * f.view(B, 1, 1, 1)` with f in {0, 1/keep_prob} in training mode,
+                the identity in eval mode or at drop_prob 0 -- but f is the injected row, not x.new_empty(shape).bernoulli_(keep_prob)."""
+            feed = None
+
+            def __init__(self, drop_prob=0.0, scale_by_keep=True):
                 super().__init__()
+                self.drop_prob, self.scale_by_keep = drop_prob, scale_by_keep
+
             def forward(self, x):
-                return x
+                if DropPath.feed is None or self.drop_prob == 0.0 or not self.training:
+                    return x
+                assert self.scale_by_keep
+                f = DropPath.feed.pop(0)
+                assert f.shape == (x.shape[0],) and all(v in (0.0, float(np.float32(1) / np.float32(1 - self.drop_prob))) for v in f.tolist())
+                return x * f.view((x.shape[0],) + (1,) * (x.ndim - 1))
         ml = types.ModuleType("timm.models.layers")
         ml.DropPath, ml.trunc_normal_ = DropPath, nn.init.trunc_normal_
         ml.to_2tuple = lambda x: tuple(x) if isinstance(x, (tuple, list)) else (x, x)
@@ -624,6 +675,62 @@ def gen_alternet():
     _whole_net_train("alternet50_b8_train", A.AlterNet50(conf), spec, alternet_ref.fill_special, 7400, recipe.images(7401, 8, 192, 192), FULL_ALTERNET50)
 
 
+# ----------------------------------------------------------------------------- the random paths of training: stochastic depth, tail dropout
+DROP_PATH, DROPOUT = 0.1, 0.5            # reference nets/AlterNet_SwinV2_FAN.py:334 (DropPath) and :667 / nets/SwinV2.py:516 (nn.Dropout())
+# seeds, not masks: both sides regenerate the draws (oracle.recipe).  keep_seed: the first from 7410 on that meets
+# oracle.alternet_ref.check_keep_factors.  dropout_seed: AlterNet's tail is bn2 -> ReLU -> Dropout, and a pre-ReLU value within fp32
+# round-off of zero that SURVIVES the mask lets an implementation take the other side of the kink (tests/wholenet.check_whole_net_train);
+# of the 10 values within 1e-4 of zero on this input the first seeds from 7430 on keep 3, which moves bn2.bias / layer4.3.norm2.weight by
+# 2-4 % of their rms (tools/kink_shift.py) -- past the rtol the tail's own tensors are held to.  8552 is the seed among 7430..37429 that
+# zeroes all 10 and keeps the fewest (one) of the values within 3e-4 in a probed channel.
+STOCH_ALTERNET50 = dict(keep_seed=7424, dropout_seed=8552)
+STOCH_SWIN34 = dict(dropout_seed=6410)
+# + step.  keep_seed: the first from 9300 on whose draws of BOTH steps meet check_keep_factors.  dropout_seed, by the same reasoning as
+# above: of the 17 pre-ReLU values of bn2 within 1e-4 of zero in step 0 (the step whose gradients the fixture pins) the first seed tried,
+# 9330, kept 11 and the product's step-0 gradient of layer2.3.attn.cpb_mlp.2.weight then sat at 5.25 % of its rms, over the 5 % the recipe
+# tests allow for kink flips; 16067 is the seed among 9330..21329 that keeps the fewest (one; six of the 39 within 3e-4)
+STOCH_RECIPE = dict(keep_seed=9314, dropout_seed=16067)
+# full gradient tensors of the stochastic fixtures: the subsets of FULL_* that keep each file under 1 MiB
+FULL_ALTERNET50_STOCH = ("conv1.weight", "layer1.0.conv1.weight", "layer2.2.attn.qkv.weight", "layer2.2.attn.cpb_mlp.0.weight",
+                         "layer2.2.attn.cpb_mlp.2.weight", "layer2.3.attn.qkv.weight", "layer2.3.attn.logit_scale", "bn2.weight", "bn3.weight",
+                         "bn3.bias")
+FULL_SWIN34_STOCH = ("conv1.weight", "layer2.0.weight", "layer3.1.attn.cpb_mlp.0.weight", "layer3.1.attn.cpb_mlp.2.weight",
+                     "layer3.1.attn.logit_scale", "layer3.1.attn.q_bias", "bn2.weight", "bn3.weight", "bn3.bias")
+
+
+def _alternet_mod():
+    """the reference's nets/AlterNet_SwinV2_FAN.py with the timm stub and an einops stub (imported, never called)"""
+    _swin_ref()
+    sys.modules.setdefault("einops", types.ModuleType("einops"))
+    if not hasattr(sys.modules["einops"], "rearrange"):
+        sys.modules["einops"].rearrange = lambda *a, **k: (_ for _ in ()).throw(RuntimeError("unused"))
+        sys.modules["einops"].repeat = sys.modules["einops"].rearrange
+    import nets.AlterNet_SwinV2_FAN as A
+    return A
+
+
+def gen_alternet_stochastic():
+    """alternet50_b8_train's pass (same weights, same images) with DropPath(0.1) and Dropout(0.5) ON, injected draws"""
+    from oracle import alternet_ref
+    A = _alternet_mod()
+    conf = types.SimpleNamespace(network="AlterNet50", emd_size=512, img_size=192)
+    keeps = recipe.keep_factors(STOCH_ALTERNET50["keep_seed"], 12, 8, 1.0 - DROP_PATH)
+    alternet_ref.check_keep_factors(keeps, "AlterNet50", 1.0 - DROP_PATH)
+    mask = recipe.dropout_mask(STOCH_ALTERNET50["dropout_seed"], (8, 512, 6, 6), DROPOUT)
+    _whole_net_train("alternet50_b8_train_stochastic", A.AlterNet50(conf), alternet_ref.alter_spec("AlterNet50"), alternet_ref.fill_special, 7400,
+                     recipe.images(7401, 8, 192, 192), FULL_ALTERNET50_STOCH, keeps=keeps, dropout_mask=mask,
+                     drop_path_rate=DROP_PATH, dropout_p=DROPOUT, **STOCH_ALTERNET50)
+
+
+def gen_swin_dropout():
+    """swin34_b8_train's pass (same weights, same images) with the tail Dropout(0.5) ON, injected mask"""
+    from oracle import swin_ref
+    S = _swin_ref()
+    mask = recipe.dropout_mask(STOCH_SWIN34["dropout_seed"], (8, 512, 7, 7), DROPOUT)
+    _whole_net_train("swin34_b8_train_dropout", S.Swin34(types.SimpleNamespace(network="Swin34", emd_size=512)), swin_ref.swin_spec("Swin34"),
+                     swin_ref.fill_special, 6400, recipe.images(6401, 8), FULL_SWIN34_STOCH, dropout_mask=mask, dropout_p=DROPOUT, **STOCH_SWIN34)
+
+
 # ----------------------------------------------------------------------------- verification metrics
 def gen_eval():
     _ref()
@@ -690,19 +797,16 @@ def gen_scheduler():
 
 
 # ----------------------------------------------------------------------------- the shipped recipe end to end (main/train.sh:12)
-def gen_recipe_alternet50():
+def gen_recipe_alternet50(stochastic=False):
     """main/train.sh:12 -- `--sample_rate 0.3 --optimizer AdamW --network AlterNet50 --lr 5e-4` -- composed as model/FR_PartialFC.py:162-193 does:
     AlterNet50 @192 encoder, F.normalize, PartialFCAdamW(rate 0.3), AdamW over [encoder, head], clip_grad_norm_(encoder, 5); two steps on fresh
-    batches of 8.  RNG-free: tail Dropout p = 0, DropPath = identity (the timm stub)."""
+    batches of 8.  RNG-free: tail Dropout p = 0, DropPath = identity (the timm stub).
+    stochastic (recipe_alternet50_adamw_rate03_stochastic): both random paths ON with injected draws, fresh per step (seed + step):
+    DropPath(0.1) through the stub's second mode, Dropout(0.5) through InjectedDropout."""
     from oracle import alternet_ref
     _, P, _ = _ref()
-    _swin_ref()
-    sys.modules.setdefault("einops", types.ModuleType("einops"))
-    if not hasattr(sys.modules["einops"], "rearrange"):
-        sys.modules["einops"].rearrange = lambda *a, **k: (_ for _ in ()).throw(RuntimeError("unused"))
-        sys.modules["einops"].repeat = sys.modules["einops"].rearrange
+    A = _alternet_mod()
     import torch.nn.functional as F
-    import nets.AlterNet_SwinV2_FAN as A
     with tempfile.TemporaryDirectory() as td:
         _init_pg(0, 1, os.path.join(td, "pg"))
         C, B, steps, rate = 256, 8, 2, 0.3
@@ -710,13 +814,16 @@ def gen_recipe_alternet50():
         enc = A.AlterNet50(conf)
         spec = alternet_ref.alter_spec("AlterNet50")
         enc.load_state_dict(alternet_ref.fill_special(recipe.fill_state(spec, 9100), spec), strict=True)
-        enc.dropout.p = 0.0
+        if not stochastic:
+            _inject(enc, None, None)
         pfc = P.PartialFCAdamW(conf, C)
         with torch.no_grad():
             pfc.weight.copy_(recipe.normal(9101, (C, 512), 0.01))
         opt = torch.optim.AdamW([{"params": enc.parameters()}, {"params": pfc.parameters()}], lr=ADAMW["lr"], weight_decay=ADAMW["wd"],
                                 eps=ADAMW["eps"], betas=ADAMW["betas"])
         arrs = dict(C=C, B=B, steps=steps, rate=rate, lr=ADAMW["lr"], wd=ADAMW["wd"], eps=ADAMW["eps"], betas=np.asarray(ADAMW["betas"]), seed=9100)
+        if stochastic:
+            arrs.update(keep_seed=STOCH_RECIPE["keep_seed"], dropout_seed=STOCH_RECIPE["dropout_seed"], drop_path_rate=DROP_PATH, dropout_p=DROPOUT)
         losses, gnorms = [], []
         names = ("conv1.weight", "layer1.0.conv1.weight", "layer2.2.attn.qkv.weight", "layer2.3.attn.cpb_mlp.2.weight", "layer3.5.conv2.weight",
                  "layer4.3.attn.proj.weight", "bn2.weight", "fc.weight", "bn3.weight")
@@ -724,7 +831,14 @@ def gen_recipe_alternet50():
             img, ids = recipe.images(9110 + 10 * st, B, 192, 192), recipe.labels(9111 + 10 * st, B, C)
             opt.zero_grad()
             enc.train()
+            if stochastic:
+                keeps = recipe.keep_factors(STOCH_RECIPE["keep_seed"] + st, 12, B, 1.0 - DROP_PATH)
+                alternet_ref.check_keep_factors(keeps, "AlterNet50", 1.0 - DROP_PATH)
+                drop_path = _inject(enc, keeps, recipe.dropout_mask(STOCH_RECIPE["dropout_seed"] + st, (B, 512, 6, 6), DROPOUT))
             feat = F.normalize(enc(img))
+            if stochastic:
+                assert drop_path.feed == [] and enc.dropout.used == st + 1
+                drop_path.feed = None
             torch.manual_seed(9200 + st)
             loss = pfc(feat, ids.clone(), opt)
             loss.backward()
@@ -745,7 +859,7 @@ def gen_recipe_alternet50():
             arrs["after." + k] = recipe.probe(esd[k].float())
         arrs.update({"after.head_weight": recipe.probe(pfc.weight, 4096), "after.head_exp_avg": recipe.probe(pfc.weight_exp_avg, 4096),
                      "after.head_exp_avg_sq": recipe.probe(pfc.weight_exp_avg_sq, 4096)})
-        save("recipe_alternet50_adamw_rate03", **arrs)
+        save("recipe_alternet50_adamw_rate03" + ("_stochastic" if stochastic else ""), **arrs)
         dist.destroy_process_group()
 
 
@@ -772,6 +886,9 @@ GENS = {
     "train_adamw": gen_train_steps_adamw,
     "train_fresh": lambda: gen_train_steps(fresh=True),
     "recipe_alternet50": gen_recipe_alternet50,
+    "alternet_stochastic": gen_alternet_stochastic,
+    "swin_dropout": gen_swin_dropout,
+    "recipe_alternet50_stochastic": lambda: gen_recipe_alternet50(stochastic=True),
 }
 
 if __name__ == "__main__":
