@@ -8,8 +8,10 @@
 //   nets/PartialFC.py:441-484 DistCrossEntropyFunc forward/backward.
 // Cross-rank steps (all-reduce MAX / SUM of the per-row scalars) are done by the host between these kernels.
 // The other margin modules of the reference (nets/ArcFace.py:5-61 CombinedMarginLoss with interclass filtering and easy_margin,
-// :94-106 CosFace) are compile-time variants of the same epilogue (template arguments MK, FILT of head_kernel).
+// :94-106 CosFace) are compile-time variants of the same epilogue (template arguments MK, FILT of head_kernel), and so is the per-row
+// margin (MG_ROWS: AdaFace, not in the reference), whose two margins per row come from adaface_margins_kernel below.
 #include "igemm_nt.h"
+#include "margin_rows.h"
 #include "frhip.h"
 
 namespace frhip {
@@ -21,9 +23,11 @@ struct MarginConstEx : MarginConst { float m3, thr; };       // CosFace margin, 
 // argument, so its kernel-argument layout and code are exactly those it had before the variants existed.
 // (named constants and a traits struct, not an unnamed enum in std::conditional: the kernels' mangled names must come out the same in the
 // host and the device compilation, and an unnamed type is numbered differently in the two)
-constexpr int MG_ARC = 0, MG_ARC_EASY = 1, MG_COS = 2;
+constexpr int MG_ARC = 0, MG_ARC_EASY = 1, MG_COS = 2, MG_ROWS = 3;
+struct MarginRows { float s, eps; const float* m_ang; const float* m_add; };      // per-row margins: [M] angular, [M] additive
 template <int MK, bool FILT> struct MarginArgOf { typedef MarginConstEx type; };
 template <> struct MarginArgOf<MG_ARC, false> { typedef MarginConst type; };
+template <> struct MarginArgOf<MG_ROWS, false> { typedef MarginRows type; };
 template <int MK, bool FILT>
 using MarginArg = typename MarginArgOf<MK, FILT>::type;
 
@@ -114,7 +118,9 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
 // ---------------------------------------------------------------------------------------------------------
 // FWD = true : partial row max / sum-exp per 64-class column group, target logit.
 // FWD = false: dT tile (compute dtype) from the recomputed cosines and the global row max / sum.
-// MK: MG_ARC (cos(theta + m), below cos(pi - m) t - m sin(pi - m)), MG_ARC_EASY (cos(theta + m) for t > 0, else t), MG_COS (t - m3).
+// MK: MG_ARC (cos(theta + m), below cos(pi - m) t - m sin(pi - m)), MG_ARC_EASY (cos(theta + m) for t > 0, else t), MG_COS (t - m3),
+// MG_ROWS (row m: every cosine clamped to [-1 + eps, 1 - eps], target cos(clamp(theta + m_ang[m], eps, pi - eps)) - m_add[m], slope 0 where
+// a clamp binds; frhip_margin_rows_t in frhip.h).
 // FILT: interclass filtering (reference nets/ArcFace.py:28-39): an element that is not its row's target and whose clamped cosine is
 // > thr is multiplied by 0 -- logit 0, which still counts in the softmax sum, and d/dcos 0 (the reference builds the mask under
 // no_grad); a row without a target on this shard (label -1) is filtered in every column.
@@ -149,6 +155,11 @@ __global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __re
         const int lab = mrow ? labels[m] : -1;
         float gm = 0.f, gs = 1.f;
         if (!FWD && mrow) { gm = rowmax[m]; gs = 1.f / rowsum[m]; }
+        [[maybe_unused]] float tlo, thi, m_ang = 0.f, m_add = 0.f;            // MG_ROWS only: the other variants keep their literals
+        if constexpr (MK == MG_ROWS) {
+            tlo = -1.f + mc.eps; thi = 1.f - mc.eps;
+            if (lab >= 0) { m_ang = mc.m_ang[m]; m_add = mc.m_add[m]; }       // lab >= 0 implies m < M
+        }
         float z[4][4];
         float vmax = -INFINITY;
 #pragma unroll
@@ -157,7 +168,9 @@ __global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __re
             for (int e = 0; e < 4; ++e) {
                 const int cls = n0 + nt * 16 + 4 * fg + e;
                 const float raw = ml.acc[nt][mt][e];
-                float t = fminf(fmaxf(raw, -1.f), 1.f);
+                float t;
+                if constexpr (MK == MG_ROWS) t = fminf(fmaxf(raw, tlo), thi);
+                else t = fminf(fmaxf(raw, -1.f), 1.f);
                 float slope = 1.f;
                 bool filtered = false;
                 if (cls == lab) {
@@ -168,6 +181,8 @@ __global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __re
                     } else if constexpr (MK == MG_ARC_EASY) {
                         const float sin_t = sqrtf(1.f - t * t);
                         if (t > 0.f) { slope = mc.cos_m + t * mc.sin_m / sin_t; t = t * mc.cos_m - sin_t * mc.sin_m; }
+                    } else if constexpr (MK == MG_ROWS) {
+                        t = rows_margin_target(t, m_ang, m_add, mc.eps, slope);
                     } else {
                         t = t - mc.m3;
                     }
@@ -183,7 +198,9 @@ __global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __re
                     float d = 0.f;
                     if (cls < g.Nout && mrow) {
                         const float p = __expf(zz - gm) * gs;
-                        const bool inside = raw >= -1.f && raw <= 1.f && !filtered;
+                        bool inside;
+                        if constexpr (MK == MG_ROWS) inside = raw >= tlo && raw <= thi;
+                        else inside = raw >= -1.f && raw <= 1.f && !filtered;
                         d = inside ? (p - (cls == lab ? 1.f : 0.f)) * gscale * mc.s * slope : 0.f;
                     }
                     ml.acc[nt][mt][e] = d;
@@ -336,6 +353,21 @@ static int head_launch_mk(const NtGeom& g, const void* ehat, const void* what, c
     return check_launch("head");
 }
 
+// the per-row margin variant (its argument is not cut out of a MarginConstEx)
+template <typename T, bool FWD>
+static int head_launch_rows(const NtGeom& g, const void* ehat, const void* what, const int* labels, const MarginRows& mc,
+                            float* pmax, float* psum, float* zt, const float* rmax, const float* rsum, float gscale,
+                            const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
+    typedef NtTile<T, 2, 2> Tile;
+    const int mtiles = (g.M + Tile::BM - 1) / Tile::BM, ntiles = (g.Nout + Tile::BN - 1) / Tile::BN;
+    const int lds = Tile::template lds_bytes<T>();
+    auto kern = head_kernel<T, FWD, MG_ROWS, false>;
+    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "head")) return FRHIP_ELAUNCH;
+    hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(256), lds, stream, g, ehat, what, labels, mc, pmax, psum,
+                       zt, rmax, rsum, gscale, upstream, dt, ldt, dtt, ldtt, mtiles, ntiles);
+    return check_launch("head");
+}
+
 template <typename T, bool FWD>
 static int head_launch(const NtGeom& g, const void* ehat, const void* what, const int* labels, const MarginConstEx& mc, int mk, bool filt,
                        float* pmax, float* psum, float* zt, const float* rmax, const float* rsum, float gscale,
@@ -391,9 +423,100 @@ static int margin_desc(const frhip_margin_t* mg, MarginConstEx& mc, int& mk, boo
     return FRHIP_OK;
 }
 
+static int margin_rows_desc(const frhip_margin_rows_t* mg, MarginRows& mc, const char* who) {
+    if (!mg || !mg->m_ang || !mg->m_add || !(mg->eps > 0.f && mg->eps < 0.5f)) {
+        set_error("%s: bad per-row margin descriptor (null pointer, or eps outside (0, 0.5))", who);
+        return FRHIP_EINVAL;
+    }
+    mc.s = mg->s; mc.eps = mg->eps; mc.m_ang = mg->m_ang; mc.m_add = mg->m_add;
+    return FRHIP_OK;
+}
+
+// AdaFace's per-row margins from the embedding norms of the global batch (frhip_adaface_margins in frhip.h).  ONE block: n is a batch
+// size, a few thousand floats; the mean and then the squared deviations from it are summed in float64.
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
+    __syncthreads();                                    // red may still be read from the previous sum
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double r = 0.0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += red[w];
+    return r;
+}
+
+__device__ __forceinline__ double safe_norm(float x) { return (double)fminf(fmaxf(x, 0.001f), 100.f); }
+
+__global__ __launch_bounds__(1024) void adaface_margins_kernel(const float* __restrict__ norms, int n, double m, double h, double t_alpha,
+                                                               double eps, int update, float* __restrict__ batch_mean,
+                                                               float* __restrict__ batch_std, float* __restrict__ m_ang,
+                                                               float* __restrict__ m_add) {
+    __shared__ double red[16];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) acc += safe_norm(norms[i]);
+    const double mean = block_sum_f64(acc, red) / (double)n;
+    acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const double dv = safe_norm(norms[i]) - mean;
+        acc += dv * dv;
+    }
+    const double sd = sqrt(block_sum_f64(acc, red) / (double)(n - 1));
+    double bm = (double)batch_mean[0], bs = (double)batch_std[0];        // every thread reads the old values ...
+    if (update) { bm = t_alpha * mean + (1.0 - t_alpha) * bm; bs = t_alpha * sd + (1.0 - t_alpha) * bs; }
+    __syncthreads();                                                     // ... before thread 0 overwrites them
+    if (update && threadIdx.x == 0) { batch_mean[0] = (float)bm; batch_std[0] = (float)bs; }
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const double k = fmin(fmax(h * (safe_norm(norms[i]) - bm) / (bs + eps), -1.0), 1.0);
+        m_ang[i] = (float)(-m * k);
+        m_add[i] = (float)(m + m * k);
+    }
+}
+
 }  // namespace frhip
 
 using namespace frhip;
+
+extern "C" int frhip_adaface_margins(const float* norms, int n, double m, double h, double t_alpha, double eps, int update,
+                                     float* batch_mean, float* batch_std, float* m_ang, float* m_add, hipStream_t stream) {
+    if (n < 2 || !norms || !batch_mean || !batch_std || !m_ang || !m_add) {
+        set_error("frhip_adaface_margins: needs n >= 2 norms (n=%d) and non-null norms, batch_mean, batch_std, m_ang, m_add", n);
+        return FRHIP_EINVAL;
+    }
+    hipLaunchKernelGGL(adaface_margins_kernel, dim3(1), dim3(n > 256 ? 1024 : 256), 0, stream, norms, n, m, h, t_alpha, eps, update,
+                       batch_mean, batch_std, m_ang, m_add);
+    return check_launch("frhip_adaface_margins");
+}
+
+extern "C" int frhip_head_fwd_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                                   int d, const frhip_margin_rows_t* margin, float* part_max, float* part_sum, float* ztarget,
+                                   float* rowmax, float* rowsum, hipStream_t stream) {
+    NtGeom g;
+    int rc = head_geom(g, dtype, n, classes, d, "frhip_head_fwd_rows");
+    if (rc) return rc;
+    MarginRows mc;
+    if ((rc = margin_rows_desc(margin, mc, "frhip_head_fwd_rows"))) return rc;
+    if (dtype == FRHIP_DT_BF16) rc = head_launch_rows<bf16_t, true>(g, ehat, what, labels, mc, part_max, part_sum, ztarget, nullptr, nullptr, 0.f, nullptr, nullptr, 0, nullptr, 0, stream);
+    else rc = head_launch_rows<float, true>(g, ehat, what, labels, mc, part_max, part_sum, ztarget, nullptr, nullptr, 0.f, nullptr, nullptr, 0, nullptr, 0, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(head_rowreduce_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, part_max, part_sum,
+                       frhip_head_groups(classes), n, rowmax, rowsum);
+    return check_launch("frhip_head_fwd_rows/rowreduce");
+}
+
+extern "C" int frhip_head_bwd_dt_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                                      int d, const frhip_margin_rows_t* margin, const float* rowmax, const float* rowsum, float gscale,
+                                      const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
+    NtGeom g;
+    int rc = head_geom(g, dtype, n, classes, d, "frhip_head_bwd_dt_rows");
+    if (rc) return rc;
+    const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
+    if (ldt < classes || (ldt % epv)) { set_error("frhip_head_bwd_dt_rows: bad dT pitch %d", ldt); return FRHIP_EINVAL; }
+    if (dtt && (ldtt < n || (ldtt % epv))) { set_error("frhip_head_bwd_dt_rows: bad transposed pitch %d", ldtt); return FRHIP_EINVAL; }
+    MarginRows mc;
+    if ((rc = margin_rows_desc(margin, mc, "frhip_head_bwd_dt_rows"))) return rc;
+    if (dtype == FRHIP_DT_BF16) return head_launch_rows<bf16_t, false>(g, ehat, what, labels, mc, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
+    return head_launch_rows<float, false>(g, ehat, what, labels, mc, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
+}
 
 extern "C" int frhip_l2norm_rows(int dtype, const float* x, void* xhat, float* norms, int rows, int d, float eps,
                                  hipStream_t stream) {

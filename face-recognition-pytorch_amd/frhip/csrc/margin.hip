@@ -5,6 +5,7 @@
 // HBM-bound row kernels: one 256-thread block per row, 16-byte accesses where the row pitch allows.
 #include "common.h"
 #include "cross_pair.h"
+#include "margin_rows.h"
 #include "frhip.h"
 
 namespace frhip {
@@ -70,6 +71,38 @@ __global__ __launch_bounds__(256) void margin_bwd_kernel(const float* __restrict
             if (t > (easy ? 0.f : theta)) gg *= cos_m + t * sin_m / sqrtf(1.f - t * t);
         }
         if (filt && ((filt[(size_t)row * words + j / 64] >> (j & 63)) & 1)) gg = 0.f;
+        gin[(size_t)row * C + j] = gg;
+    }
+}
+
+// Per-row margins (frhip_margin_rows_t, AdaFace) on explicit logits.  NOT in place: every element is clamped to [-1 + eps, 1 - eps] and
+// the gradient is 0 where the clamp binds, which the backward decides from the caller's untouched input.
+__global__ __launch_bounds__(256) void margin_fwd_rows_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                              int C, float s, float eps, const float* __restrict__ m_ang,
+                                                              const float* __restrict__ m_add, float* __restrict__ out) {
+    const int row = blockIdx.x;
+    const int64_t lab = labels[row];
+    for (int j = threadIdx.x; j < C; j += 256) {
+        float t = fminf(fmaxf(logits[(size_t)row * C + j], -1.f + eps), 1.f - eps), slope;
+        if (j == lab) t = rows_margin_target(t, m_ang[row], m_add[row], eps, slope);
+        out[(size_t)row * C + j] = t * s;
+    }
+}
+
+__global__ __launch_bounds__(256) void margin_bwd_rows_kernel(const float* __restrict__ gout, const float* __restrict__ logits,
+                                                              const int64_t* __restrict__ labels, int C, float s, float eps,
+                                                              const float* __restrict__ m_ang, const float* __restrict__ m_add,
+                                                              float* __restrict__ gin) {
+    const int row = blockIdx.x;
+    const int64_t lab = labels[row];
+    for (int j = threadIdx.x; j < C; j += 256) {
+        const float raw = logits[(size_t)row * C + j];
+        float gg = (raw >= -1.f + eps && raw <= 1.f - eps) ? gout[(size_t)row * C + j] * s : 0.f;
+        if (j == lab) {
+            float slope;
+            rows_margin_target(fminf(fmaxf(raw, -1.f + eps), 1.f - eps), m_ang[row], m_add[row], eps, slope);
+            gg *= slope;
+        }
         gin[(size_t)row * C + j] = gg;
     }
 }
@@ -161,6 +194,32 @@ extern "C" int frhip_margin_bwd(const float* gout, const int64_t* labels, const 
                                 float m, int kind, float* gin, hipStream_t stream) {
     const frhip_margin_t mg = {kind, 0, s, m, 0.f};
     return frhip_margin_bwd_ex(gout, labels, tsave, nullptr, n, c, &mg, gin, stream);
+}
+
+static int margin_rows_args(const frhip_margin_rows_t* mg, const void* a, const void* b, const void* c, const void* d, const char* who) {
+    if (!mg || !mg->m_ang || !mg->m_add || !(mg->eps > 0.f && mg->eps < 0.5f) || !a || !b || !c || !d) {
+        set_error("%s: null pointer, or eps outside (0, 0.5)", who);
+        return FRHIP_EINVAL;
+    }
+    return FRHIP_OK;
+}
+
+extern "C" int frhip_margin_fwd_rows(const float* logits, const int64_t* labels, int n, int c, const frhip_margin_rows_t* margin,
+                                     float* out, hipStream_t stream) {
+    if (n <= 0) return FRHIP_OK;
+    if (margin_rows_args(margin, logits, labels, out, out, "frhip_margin_fwd_rows")) return FRHIP_EINVAL;
+    hipLaunchKernelGGL(margin_fwd_rows_kernel, dim3(n), dim3(256), 0, stream, logits, labels, c, margin->s, margin->eps, margin->m_ang,
+                       margin->m_add, out);
+    return check_launch("frhip_margin_fwd_rows");
+}
+
+extern "C" int frhip_margin_bwd_rows(const float* gout, const float* logits, const int64_t* labels, int n, int c,
+                                     const frhip_margin_rows_t* margin, float* gin, hipStream_t stream) {
+    if (n <= 0) return FRHIP_OK;
+    if (margin_rows_args(margin, gout, logits, labels, gin, "frhip_margin_bwd_rows")) return FRHIP_EINVAL;
+    hipLaunchKernelGGL(margin_bwd_rows_kernel, dim3(n), dim3(256), 0, stream, gout, logits, labels, c, margin->s, margin->eps,
+                       margin->m_ang, margin->m_add, gin);
+    return check_launch("frhip_margin_bwd_rows");
 }
 
 extern "C" int frhip_rows_max(const float* x, int n, int c, float* rowmax, hipStream_t stream) {

@@ -1,0 +1,25 @@
+// Target element of the per-row margin (frhip_margin_rows_t in frhip.h), shared by the fused head (head.hip) and the explicit-logit
+// kernels (margin.hip) so the two cannot drift apart.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace frhip {
+
+// t: the target cosine, already clamped to [-1 + eps, 1 - eps].  Returns cos(clamp(theta + m_ang, eps, pi - eps)) - m_add and sets
+// slope = d/dt = sin(theta + m_ang) / sin(theta), 0 where the clip of the angle binds.
+// u = theta + m_ang only decides the branch; inside the clip cos(u) = t cos(m_ang) - sin(theta) sin(m_ang) and
+// sin(u) / sin(theta) = cos(m_ang) + t sin(m_ang) / sin(theta): the ArcFace forms, nothing goes back through acos.
+__device__ __forceinline__ float rows_margin_target(float t, float m_ang, float m_add, float eps, float& slope) {
+    const float pi = 3.14159265358979f, u = acosf(t) + m_ang;
+    if (u < eps || u > pi - eps) {
+        slope = 0.f;
+        return (u < eps ? cosf(eps) : -cosf(eps)) - m_add;
+    }
+    float sa, ca;
+    sincosf(m_ang, &sa, &ca);
+    const float sin_t = sqrtf((1.f - t) * (1.f + t));      // 1 - t is exact near t = 1 - eps, where 1 - t * t would lose five digits
+    slope = ca + t * sa / sin_t;
+    return t * ca - sin_t * sa - m_add;
+}
+
+}  // namespace frhip

@@ -770,8 +770,40 @@ def _margin_desc(margin):
     return _MarginDesc(int(kind), int(bool(easy)), float(s), float(m), float(thr))
 
 
+class _MarginRowsDesc(ctypes.Structure):
+    _fields_ = [("s", ctypes.c_float), ("eps", ctypes.c_float), ("m_ang", ctypes.c_void_p), ("m_add", ctypes.c_void_p)]
+
+
+def _is_rows(margin):
+    """per-row margins (frhip_margin_rows_t), e.g. nets.ArcFace.RowMargins: fields s, eps and the device vectors m_ang, m_add [n] fp32"""
+    return hasattr(margin, "m_ang")
+
+
+def _margin_rows_desc(margin, n):
+    for v in (margin.m_ang, margin.m_add):
+        if v.dtype != torch.float32 or v.numel() != n:
+            raise ValueError("per-row margins must be float32 vectors with one entry per row (%d), got %s %s"
+                             % (n, v.dtype, tuple(v.shape)))
+    return _MarginRowsDesc(float(margin.s), float(margin.eps), _p(margin.m_ang), _p(margin.m_add))
+
+
+def adaface_margins(norms, m, h, t_alpha, eps, batch_mean, batch_std, update):
+    """AdaFace's per-row margins (m_ang, m_add) from the embedding norms [n] of the global batch in ONE launch (frhip_adaface_margins);
+    update: the running batch_mean / batch_std (device scalars, fp32) are advanced in place first, else only read.  No host sync."""
+    _need_cuda("adaface_margins", norms=norms, batch_mean=batch_mean, batch_std=batch_std)
+    for nm, t in (("norms", norms), ("batch_mean", batch_mean), ("batch_std", batch_std)):
+        if t.dtype != torch.float32:
+            raise ValueError("adaface_margins: %s must be float32, got %s" % (nm, t.dtype))
+    n = norms.numel()
+    out = torch.empty((2, n), dtype=torch.float32, device=norms.device)
+    check(lib().frhip_adaface_margins(_p(norms), n, m, h, t_alpha, eps, int(bool(update)), _p(batch_mean), _p(batch_std),
+                                      _p(out[0]), _p(out[1]), _s()), "frhip_adaface_margins")
+    return out[0], out[1]
+
+
 def head_fwd(ehat, what, labels_i32, s, m, margin=None):
-    """margin=None: ArcFace(s, m) (frhip_head_fwd); else a (kind, easy, s, m, filter_thr) descriptor (frhip_head_fwd_ex)"""
+    """margin=None: ArcFace(s, m) (frhip_head_fwd); a (kind, easy, s, m, filter_thr) descriptor (frhip_head_fwd_ex); or per-row
+    margins (s, eps, m_ang, m_add), e.g. nets.ArcFace.RowMargins (frhip_head_fwd_rows)"""
     n, d = ehat.shape
     classes = what.shape[0]
     groups = lib().frhip_head_groups(classes)
@@ -784,6 +816,10 @@ def head_fwd(ehat, what, labels_i32, s, m, margin=None):
     if margin is None:
         check(lib().frhip_head_fwd(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, s, m, _p(pm), _p(ps),
                                    _p(zt), _p(rmax), _p(rsum), _s()), "frhip_head_fwd")
+    elif _is_rows(margin):
+        desc = _margin_rows_desc(margin, n)
+        check(lib().frhip_head_fwd_rows(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, ctypes.byref(desc), _p(pm),
+                                        _p(ps), _p(zt), _p(rmax), _p(rsum), _s()), "frhip_head_fwd_rows")
     else:
         desc = _margin_desc(margin)
         check(lib().frhip_head_fwd_ex(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, ctypes.byref(desc), _p(pm),
@@ -839,6 +875,10 @@ def head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, gscale, upstream=None,
     if margin is None:
         check(lib().frhip_head_bwd_dt(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, s, m, _p(rmax),
                                       _p(rsum), gscale, _p(upstream), _p(dt), ldt, _p(dtt), ldtt, _s()), "frhip_head_bwd_dt")
+    elif _is_rows(margin):
+        desc = _margin_rows_desc(margin, n)
+        check(lib().frhip_head_bwd_dt_rows(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, ctypes.byref(desc), _p(rmax),
+                                           _p(rsum), gscale, _p(upstream), _p(dt), ldt, _p(dtt), ldtt, _s()), "frhip_head_bwd_dt_rows")
     else:
         desc = _margin_desc(margin)
         check(lib().frhip_head_bwd_dt_ex(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, ctypes.byref(desc), _p(rmax),
@@ -877,6 +917,24 @@ def margin_bwd_ex(gout, labels_i64, tsave, filt, margin):
     gin = torch.empty_like(gout)
     check(lib().frhip_margin_bwd_ex(_p(gout), _p(labels_i64), _p(tsave), _p(filt), n, c, ctypes.byref(desc), _p(gin), _s()),
           "frhip_margin_bwd_ex")
+    return gin
+
+
+def margin_fwd_rows(logits, labels_i64, margin):
+    """out [n, c] = s x per-row margin of logits (margin: s, eps, m_ang, m_add); logits stay untouched (the backward reads them)"""
+    n, c = logits.shape
+    desc = _margin_rows_desc(margin, n)
+    out = torch.empty_like(logits)
+    check(lib().frhip_margin_fwd_rows(_p(logits), _p(labels_i64), n, c, ctypes.byref(desc), _p(out), _s()), "frhip_margin_fwd_rows")
+    return out
+
+
+def margin_bwd_rows(gout, logits, labels_i64, margin):
+    n, c = gout.shape
+    desc = _margin_rows_desc(margin, n)
+    gin = torch.empty_like(gout)
+    check(lib().frhip_margin_bwd_rows(_p(gout), _p(logits), _p(labels_i64), n, c, ctypes.byref(desc), _p(gin), _s()),
+          "frhip_margin_bwd_rows")
     return gin
 
 

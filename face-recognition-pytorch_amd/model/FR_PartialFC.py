@@ -41,6 +41,30 @@ def normalize(x):
     return _NormalizeFn.apply(x)
 
 
+class _NormalizeNormsFn(torch.autograd.Function):
+    """_NormalizeFn that also hands out the row norms it computes (no gradient through them): what a margin with needs_norms
+    (nets.ArcFace.AdaFace) derives its per-row margins from."""
+
+    @staticmethod
+    def forward(ctx, x):
+        from frhip import ops
+        xh, nrm = ops.l2norm_rows(x.contiguous().float(), torch.float32)
+        ctx.save_for_backward(xh, nrm)
+        ctx.mark_non_differentiable(nrm)
+        return xh, nrm
+
+    @staticmethod
+    def backward(ctx, g, _):
+        from frhip import ops
+        xh, nrm = ctx.saved_tensors
+        return ops.l2norm_bwd(g.contiguous().float(), xh, nrm)
+
+
+def normalize_with_norms(x):
+    """-> (F.normalize(x) rows, their norms before normalisation [N], detached)"""
+    return _NormalizeNormsFn.apply(x)
+
+
 class Model(nn.Module):
     def __init__(self, conf, logger=None, stage="train"):
         super().__init__()
@@ -75,8 +99,8 @@ class Model(nn.Module):
                 else:
                     self.encoder = DDP(self.encoder, broadcast_buffers=False, device_ids=[conf.local_rank])
             head_mod = importlib.import_module("nets.%s" % getattr(conf, "loss", "PartialFC"))
-            # conf.margin_loss (optional, not in the reference): a callable (s, m) -> margin module, e.g. nets.ArcFace.CosFace;
-            # absent = the reference's ArcFace
+            # conf.margin_loss (optional, not in the reference): a callable (s, m) -> margin module, e.g. nets.ArcFace.CosFace or
+            # nets.ArcFace.AdaFace; absent = the reference's ArcFace
             margin = {"margin_loss": conf.margin_loss} if getattr(conf, "margin_loss", None) is not None else {}
             if conf.optimizer == "SGD":
                 self.loss = head_mod.PartialFC(conf=conf, num_classes=conf.n_classes, **margin)
@@ -102,9 +126,14 @@ class Model(nn.Module):
         self.encoder.train()
         if hasattr(self.loss, "prepare"):          # label all-gather + the one sync sampling needs, before the GPU gets busy
             self.loss.prepare(id_, self.opt)
-        feat = normalize(self.forward(img))
+        extra = {}
+        if getattr(getattr(self.loss, "margin_softmax", None), "needs_norms", False):
+            # AdaFace: the head is fed unit rows, so the norms its margins depend on are the ones this normalisation divides by
+            feat, extra["norms"] = normalize_with_norms(self.forward(img))
+        else:
+            feat = normalize(self.forward(img))
         self.loss.train()
-        loss = self.loss(feat, id_, self.opt)
+        loss = self.loss(feat, id_, self.opt, **extra)
         if hasattr(self.opt, "step_group_early") and hasattr(self.loss, "arm_early_update"):
             # the clip below covers the ENCODER only (reference :181) and step() follows this one backward(): the head's parameter
             # group may be updated as soon as its gradient exists, beside the backbone's backward pass

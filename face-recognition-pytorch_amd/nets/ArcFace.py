@@ -6,6 +6,10 @@ cosines are modified IN PLACE at the target entries (labels [N,1] or [N] int64, 
 scaled tensor is returned.  On the MI355X the work is one HIP row kernel (frhip_margin_fwd / _bwd) wrapped in an
 autograd node.
 
+`AdaFace(s, m, h, t_alpha)` (Kim et al., CVPR 2022; not in the reference) gives every row its own margin, derived from the norm of that
+row's embedding before normalisation: `forward(logits, labels, norms)`.  It clamps EVERY cosine, so unlike the others it returns a new
+tensor and leaves `logits` untouched.
+
 Inside PartialFC the margin is not applied through this `forward`: it lives in the epilogue of the fused cos-theta
 MFMA kernel (frhip_head_fwd / frhip_head_fwd_ex), which only reads the module's constants through `margin_of`, so the
 [N, C] logits this `forward` would overwrite never exist in HBM on the training hot path.
@@ -21,12 +25,19 @@ ARCFACE, COSFACE = 0, 1          # frhip_margin_t.kind
 # scale s, margin m, interclass filtering threshold filter_thr (0 = off).
 Margin = collections.namedtuple("Margin", "kind easy s m filter_thr")
 
-SUPPORTED = "ArcFace, CosFace, CombinedMarginLoss (ArcFace m1 == 1, m3 == 0 or CosFace m3 > 0)"
+# AdaFace: what margin_of returns for it (the constants of the module), and what the kernels take once frhip_adaface_margins has turned
+# the batch's norms into margins: scale, clamp width and the device vectors [N] of angular / additive margins (frhip_margin_rows_t).
+AdaMargin = collections.namedtuple("AdaMargin", "s m h t_alpha eps")
+RowMargins = collections.namedtuple("RowMargins", "s eps m_ang m_add")
+
+SUPPORTED = "ArcFace, CosFace, CombinedMarginLoss (ArcFace m1 == 1, m3 == 0 or CosFace m3 > 0), AdaFace"
 
 
 def margin_of(module):
     """-> Margin of a margin module of this package, read from its attributes NOW (so a later `easy_margin = True` counts, as in
-    the reference, whose modules read their attributes in forward).  NotImplementedError for any other module."""
+    the reference, whose modules read their attributes in forward); AdaMargin for AdaFace.  NotImplementedError for any other module."""
+    if isinstance(module, AdaFace):
+        return AdaMargin(float(module.s), float(module.m), float(module.h), float(module.t_alpha), float(module.eps))
     if isinstance(module, ArcFace):
         return Margin(ARCFACE, bool(module.easy_margin), float(module.scale), float(module.margin), 0.0)
     if isinstance(module, CosFace):
@@ -44,7 +55,7 @@ def margin_of(module):
 
 
 def is_plain_arcface(mg):
-    return mg.kind == ARCFACE and not mg.easy and mg.filter_thr == 0.0
+    return isinstance(mg, Margin) and mg.kind == ARCFACE and not mg.easy and mg.filter_thr == 0.0
 
 
 class _MarginFn(torch.autograd.Function):
@@ -124,3 +135,59 @@ class CombinedMarginLoss(torch.nn.Module):
 
     def forward(self, logits, labels):
         return _MarginFn.apply(logits, labels, margin_of(self))
+
+
+class _RowMarginFn(torch.autograd.Function):
+    """per-row margins on explicit logits (frhip_margin_fwd_rows / _bwd_rows); no gradient to the margins"""
+
+    @staticmethod
+    def forward(ctx, logits, labels, rows):
+        from frhip import ops
+        if not logits.is_cuda:
+            raise RuntimeError("nets.ArcFace (frhip): logits must live on the MI355X; there is no CPU path")
+        lab = labels.reshape(-1).long().contiguous()
+        ctx.save_for_backward(logits, lab, rows.m_ang, rows.m_add)        # the input itself: autograd then notices a later in-place write
+        ctx.s, ctx.eps = rows.s, rows.eps
+        return ops.margin_fwd_rows(logits.detach().float().contiguous(), lab, rows)
+
+    @staticmethod
+    def backward(ctx, g):
+        from frhip import ops
+        logits, lab, m_ang, m_add = ctx.saved_tensors
+        return ops.margin_bwd_rows(g.contiguous().float(), logits.detach().float().contiguous(), lab,
+                                   RowMargins(ctx.s, ctx.eps, m_ang, m_add)), None, None
+
+
+class AdaFace(torch.nn.Module):
+    """Quality-adaptive margin (AdaFace): with sn = clip(norm, 0.001, 100) and k = clip(h (sn - batch_mean) / (batch_std + eps), -1, 1),
+    row i's target logit is s (cos(clip(theta + a_i, eps, pi - eps)) - b_i), a_i = -m k_i, b_i = m + m k_i; every cosine is clamped to
+    [-1 + eps, 1 - eps] first and every logit is x s.  batch_mean / batch_std are running statistics of the GLOBAL batch's norms
+    (momentum t_alpha, std unbiased), advanced in training mode before they are used and only read in eval mode.  No gradient flows
+    through the norms.  needs_norms tells PartialFC / Model to hand the norms over."""
+    kind = "adaface"
+    needs_norms = True
+    eps = 1e-3
+
+    def __init__(self, s=64.0, m=0.4, h=0.333, t_alpha=0.01):
+        super().__init__()
+        self.s, self.m, self.h, self.t_alpha = s, m, h, t_alpha
+        self.scale, self.margin = s, m
+        self.register_buffer("batch_mean", torch.ones(1) * 20.0)
+        self.register_buffer("batch_std", torch.ones(1) * 100.0)
+
+    def row_margins(self, norms, kernels=None):
+        """norms [N] of the global batch (fp32, detached) -> RowMargins; in training mode the running buffers are advanced first.
+        ONE launch of frhip_adaface_margins, no host synchronisation.  kernels: PartialFC's kernel object (tests swap in a double)."""
+        mg = margin_of(self)
+        norms = norms.detach().reshape(-1).float().contiguous()
+        fn = kernels.adaface_margins if kernels is not None else _hip_adaface_margins
+        m_ang, m_add = fn(norms, mg, self.batch_mean, self.batch_std, self.training)
+        return RowMargins(mg.s, mg.eps, m_ang, m_add)
+
+    def forward(self, logits: torch.Tensor, labels: torch.Tensor, norms: torch.Tensor):
+        return _RowMarginFn.apply(logits, labels, self.row_margins(norms))
+
+
+def _hip_adaface_margins(norms, mg, batch_mean, batch_std, update):
+    from frhip import ops
+    return ops.adaface_margins(norms, mg.m, mg.h, mg.t_alpha, mg.eps, batch_mean, batch_std, update)

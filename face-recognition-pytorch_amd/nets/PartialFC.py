@@ -11,7 +11,7 @@ What runs where
     [num_local] vectors; the uniform draws come from torch's CPU generator exactly like the reference (:110), so
     `weight_index` is reproducible from the CPU seed alone;
   * everything floating-point is libfrhip: row l2-normalise, ONE fused kernel for cos-theta GEMM -> clamp ->
-    margin (ArcFace; CosFace, easy margin, interclass filtering as kernel variants) -> x s -> per-row max / sum-exp (logits never reach HBM), a recompute kernel that emits
+    margin (ArcFace; CosFace, easy margin, interclass filtering, AdaFace's per-row margins as kernel variants) -> x s -> per-row max / sum-exp (logits never reach HBM), a recompute kernel that emits
     d loss / d cos once, two MFMA TN GEMMs for dW and dE, normalise-backward, and row gather / scatter of the
     sampled class centres;
   * cross-rank traffic is torch.distributed (backend "nccl" = RCCL over xGMI), FOUR collectives per step on
@@ -19,7 +19,8 @@ What runs where
     path), an all-gather of the embeddings (:182), ONE all-gather of the packed per-row {max, sum-exp, target logit}
     triples that every rank merges itself (the reference issues all-reduce MAX, SUM, SUM, :448-459), and ONE
     reduce-scatter of dE issued before the dW GEMM so the two overlap (the reference loops world_size reduce() calls,
-    :510-519).
+    :510-519).  AdaFace alone adds a fifth, small one: an all-gather of the rows' norms ([N] floats), from which every rank derives the
+    same per-row margins and the same running statistics (frhip_adaface_margins, one launch).
 The floating-point steps sit behind `HipHeadKernels`; tests on CPU/gloo swap in an oracle-backed double to
 exercise the distributed host logic without a GPU.  There is no built-in CPU fallback.
 """
@@ -30,7 +31,8 @@ from typing import Callable
 import torch
 from torch import distributed
 
-from .ArcFace import SUPPORTED as SUPPORTED_MARGINS, ArcFace, CombinedMarginLoss, CosFace, is_plain_arcface, margin_of
+from .ArcFace import (SUPPORTED as SUPPORTED_MARGINS, AdaFace, AdaMargin, ArcFace, CombinedMarginLoss, CosFace, RowMargins,
+                      is_plain_arcface, margin_of)
 
 
 import os
@@ -52,8 +54,12 @@ class HipHeadKernels:
         return self.ops.l2norm_rows(x.contiguous(), self.dtype)          # (xhat, norms)
 
     def forward_stats(self, ehat, what, labels_i32, s, m, margin=None):
-        """margin: None = ArcFace(s, m); else a nets.ArcFace.Margin (CosFace, easy margin, interclass filtering)"""
+        """margin: None = ArcFace(s, m); else a nets.ArcFace.Margin (CosFace, easy margin, interclass filtering) or RowMargins (AdaFace)"""
         return self.ops.head_fwd(ehat, what, labels_i32, s, m, margin=margin)     # (ztarget, rowmax, rowsum) of this shard
+
+    def adaface_margins(self, norms, mg, batch_mean, batch_std, update):
+        """-> (m_ang, m_add) [N] from the global batch's norms; update: batch_mean / batch_std are advanced in place first"""
+        return self.ops.adaface_margins(norms, mg.m, mg.h, mg.t_alpha, mg.eps, batch_mean, batch_std, update)
 
     def rescale(self, rowsum, local_max, global_max):
         self.ops.head_rescale(rowsum, local_max, global_max)
@@ -162,7 +168,9 @@ class _MarginSoftmaxFn(torch.autograd.Function):
     Arithmetic: SURVEY.md Appendix A steps 1-7 (nets/PartialFC.py:182, :198-207, nets/ArcFace.py:76-91, :441-484, :504-522)."""
 
     @staticmethod
-    def forward(ctx, local_embeddings, weight_activated, labels_i32, kern, s, m, world_size, collectives, margin=None):
+    def forward(ctx, local_embeddings, weight_activated, labels_i32, kern, s, m, world_size, collectives, margin=None, adaface=None):
+        """adaface: None, or (AdaFace module, this rank's norms [rows]) -- the per-row margins are then derived here, from the norms of
+        the global batch in rank order, and `margin` is ignored"""
         local_embeddings = local_embeddings.contiguous()
         rows, dim = local_embeddings.shape
         if collectives:                                                         # :182 (C1)
@@ -173,6 +181,14 @@ class _MarginSoftmaxFn(torch.autograd.Function):
         what, wnorm = kern.normalize(weight_activated)
         # margin None (ArcFace, the reference default): the kernel interface is called exactly as before the other margins existed
         extra = {} if margin is None else {"margin": margin}
+        row_vecs = ()
+        if adaface is not None:
+            module, local_norms = adaface
+            local_norms = local_norms.detach().reshape(-1).float().contiguous()
+            norms = _all_gather_flat(local_norms.new_empty(world_size * rows), local_norms) if collectives else local_norms
+            rm = module.row_margins(norms, kern)            # ONE launch; advances the running buffers in training mode
+            extra, row_vecs = {"margin": rm}, (rm.m_ang, rm.m_add)
+            ctx.row_consts = (rm.s, rm.eps)
         zt, rmax, rsum = kern.forward_stats(ehat, what, labels_i32, s, m, **extra)
         if collectives:                                                         # :448, :453, :459 (C3-C5) in one exchange
             mine = kern.pack_stats(zt, labels_i32, rmax, rsum)
@@ -182,17 +198,18 @@ class _MarginSoftmaxFn(torch.autograd.Function):
             q = kern.target_prob(zt, labels_i32, rmax, rsum)
         loss = kern.loss(q)
         ctx.kern, ctx.s, ctx.m, ctx.world_size, ctx.collectives, ctx.rows = kern, s, m, world_size, collectives, rows
-        ctx.extra = extra
-        ctx.save_for_backward(ehat, enorm, what, wnorm, labels_i32, rmax, rsum)
+        ctx.extra = {} if row_vecs else extra
+        ctx.save_for_backward(ehat, enorm, what, wnorm, labels_i32, rmax, rsum, *row_vecs)
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, grad_loss):
-        ehat, enorm, what, wnorm, labels_i32, rmax, rsum = ctx.saved_tensors
+        ehat, enorm, what, wnorm, labels_i32, rmax, rsum, *row_vecs = ctx.saved_tensors
+        extra = {"margin": RowMargins(*ctx.row_consts, *row_vecs)} if row_vecs else ctx.extra
         up = grad_loss.reshape(1).float().contiguous()
         if not ctx.collectives:
-            d_e, d_w = ctx.kern.backward(ehat, enorm, what, wnorm, labels_i32, ctx.s, ctx.m, rmax, rsum, ehat.shape[0], up, **ctx.extra)
-            return d_e, d_w, None, None, None, None, None, None, None
+            d_e, d_w = ctx.kern.backward(ehat, enorm, what, wnorm, labels_i32, ctx.s, ctx.m, rmax, rsum, ehat.shape[0], up, **extra)
+            return d_e, d_w, None, None, None, None, None, None, None, None
         # :504-522 (C6): reduce-scatter(SUM) of dE, x world_size (folded into the normalise-backward's scale); issued as soon
         # as dE is enqueued so that it runs beside the dW GEMM
         pending = []
@@ -202,11 +219,11 @@ class _MarginSoftmaxFn(torch.autograd.Function):
             pending.append(_reduce_scatter_sum(d_e, rank, ctx.rows, async_op=True))
 
         _, d_w = ctx.kern.backward(ehat, enorm, what, wnorm, labels_i32, ctx.s, ctx.m, rmax, rsum, ehat.shape[0], up,
-                                   e_scale=float(ctx.world_size), on_de=start, **ctx.extra)
+                                   e_scale=float(ctx.world_size), on_de=start, **extra)
         d_local, work = pending[0]
         if work is not None:
             work.wait()
-        return d_local, d_w, None, None, None, None, None, None, None
+        return d_local, d_w, None, None, None, None, None, None, None, None
 
 
 class DistCrossEntropyFunc(torch.autograd.Function):
@@ -282,7 +299,7 @@ class _PartialFCBase(torch.nn.Module):
             self.margin_softmax = margin_loss(conf.loss_s, conf.loss_m)
         else:
             raise
-        if not isinstance(self.margin_softmax, (ArcFace, CosFace, CombinedMarginLoss)):
+        if not isinstance(self.margin_softmax, (ArcFace, CosFace, CombinedMarginLoss, AdaFace)):
             raise NotImplementedError("the fused head kernel implements the margin modules %s, not %s"
                                       % (SUPPORTED_MARGINS, type(self.margin_softmax).__name__))
         self._kernels = kernels
@@ -467,7 +484,17 @@ class _PartialFCBase(torch.nn.Module):
             for nm in self._state_names:
                 k.scatter_rows(getattr(self, "weight_activated_" + nm), self.weight_index, getattr(self, "weight_" + nm))
 
-    def forward(self, local_embeddings, local_labels, optimizer):
+    def forward(self, local_embeddings, local_labels, optimizer, norms=None):
+        """norms: this rank's [B] embedding norms BEFORE normalisation, for a margin that derives per-row margins from them (AdaFace,
+        `margin_softmax.needs_norms`); required there, refused elsewhere.  No gradient flows through them."""
+        needs_norms = bool(getattr(self.margin_softmax, "needs_norms", False))
+        if needs_norms and norms is None:
+            raise ValueError("%s derives its margins from the embedding norms: call forward(local_embeddings, local_labels, optimizer, "
+                             "norms=<[B] norms before normalisation>)" % type(self.margin_softmax).__name__)
+        if norms is not None and not needs_norms:
+            raise ValueError("norms were given, but %s does not take them" % type(self.margin_softmax).__name__)
+        if needs_norms and norms.numel() != local_embeddings.size(0):
+            raise ValueError("norms must hold one value per local embedding (%d), got %d" % (local_embeddings.size(0), norms.numel()))
         local_labels.squeeze_()
         prep, self._prep = getattr(self, "_prep", None), None
         if prep is not None and prep[0] != local_labels.data_ptr():
@@ -506,9 +533,12 @@ class _PartialFCBase(torch.nn.Module):
         mg = margin_of(self.margin_softmax)
         s, m = mg.s, mg.m
         margin = None if is_plain_arcface(mg) else mg
+        # AdaFace: its per-row margins are derived inside the autograd node, from the gathered norms; every other margin makes the call
+        # it made before per-row margins existed
+        tail = (None, (self.margin_softmax, norms)) if isinstance(mg, AdaMargin) else (margin,)
         if ready is not None and ready.numel() == n_global:      # everything label-side was done by prepare()
             return _MarginSoftmaxFn.apply(local_embeddings, self.weight_activated, ready, self.kernels, s, m,
-                                          self.world_size, collectives, margin)
+                                          self.world_size, collectives, *tail)
         n_pos = None
         if prep is not None and prep[1].numel() == n_global:
             labels, n_pos = prep[1], prep[2]                      # gathered at the start of the step by prepare()
@@ -524,7 +554,7 @@ class _PartialFCBase(torch.nn.Module):
         if self.sample_rate < 1:
             self.sample(labels, index_positive, optimizer, n_pos)
         return _MarginSoftmaxFn.apply(local_embeddings, self.weight_activated, labels.view(-1).to(torch.int32).contiguous(),
-                                      self.kernels, s, m, self.world_size, collectives, margin)
+                                      self.kernels, s, m, self.world_size, collectives, *tail)
 
     def arm_early_update(self, optimizer):
         """Call between forward() and loss.backward() of a step whose gradient clip leaves the class centres out and that calls
@@ -568,6 +598,13 @@ class _PartialFCBase(torch.nn.Module):
         return destination
 
     def load_state_dict(self, state_dict, strict: bool = True):
+        # the running statistics of a margin that has them (AdaFace; state_dict() carries them as margin_softmax.*); a checkpoint
+        # written without them loads as the initial values
+        if isinstance(self.margin_softmax, AdaFace):
+            for name, init in (("batch_mean", 20.0), ("batch_std", 100.0)):
+                buf, src = getattr(self.margin_softmax, name), state_dict.get("margin_softmax." + name)
+                with torch.no_grad():
+                    buf.copy_(src.to(buf.device).reshape(buf.shape)) if src is not None else buf.fill_(init)
         if self.sample_rate < 1:
             self.weight = state_dict["weight"].to(self.weight.device)
             for nm in self._state_names:

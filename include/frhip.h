@@ -314,6 +314,28 @@ int frhip_head_bwd_dt_ex(int dtype, const void* ehat, const void* what, const in
                          int d, const frhip_margin_t* margin, const float* rowmax, const float* rowsum, float gscale,
                          const float* upstream, void* dt, int ldt, void* dtt, int ldtt, frhip_stream_t stream);
 
+/* Per-row margins (not in the reference: AdaFace, Kim et al., CVPR 2022): the target element of row i gets the angular margin
+ * m_ang[i] and the additive margin m_add[i] (device vectors of n floats, indexed by row of the global batch):
+ *   every cosine t = clamp(raw, -1 + eps, 1 - eps) (gradient 0 where the clamp binds); non-target logit s t;
+ *   target: u = acos(t) + m_ang[i], logit s (cos(clamp(u, eps, pi - eps)) - m_add[i]), d/dt = s sin(u) / sqrt(1 - t^2) while
+ *   eps <= u <= pi - eps, else 0.  Rows whose label is -1 on this shard have no target. */
+typedef struct { float s, eps; const float* m_ang; const float* m_add; } frhip_margin_rows_t;
+/* AdaFace's margins from the embedding norms of the global batch, ONE launch, no host synchronisation (capturable):
+ *   sn = clamp(norms, 0.001, 100); mean, std (unbiased, n - 1) of sn, summed in float64 in two passes;
+ *   update != 0 (training): batch_mean <- t_alpha mean + (1 - t_alpha) batch_mean, batch_std likewise, written back (fp32) and used
+ *   in this same call; update == 0 (eval): the buffers are only read;
+ *   k = clamp(h (sn - batch_mean) / (batch_std + eps), -1, 1); m_ang = -m k; m_add = m + m k.
+ * batch_mean, batch_std: device scalars (fp32).  n < 2 or a null pointer: FRHIP_EINVAL, nothing is launched. */
+int frhip_adaface_margins(const float* norms, int n, double m, double h, double t_alpha, double eps, int update, float* batch_mean,
+                          float* batch_std, float* m_ang, float* m_add, frhip_stream_t stream);
+/* frhip_head_fwd / frhip_head_bwd_dt with per-row margins: one more instantiation of the same kernel (two floats read per row) */
+int frhip_head_fwd_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                        int d, const frhip_margin_rows_t* margin, float* part_max, float* part_sum, float* ztarget,
+                        float* rowmax, float* rowsum, frhip_stream_t stream);
+int frhip_head_bwd_dt_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                           int d, const frhip_margin_rows_t* margin, const float* rowmax, const float* rowsum, float gscale,
+                           const float* upstream, void* dt, int ldt, void* dtt, int ldtt, frhip_stream_t stream);
+
 /* ---- bn1 -> relu -> conv2 of a BasicBlock (nets/resnet.py:91-93) WITHOUT the activated tensor: the BatchNorm-apply + ReLU
  * is folded into the operand path of the convolution (forward) and of its weight gradient, which read the saved BatchNorm
  * INPUT x and form relu(x * in_scale[c] + in_shift[c]) in LDS.  bf16, 3x3 / stride 1 / pad 1; *_fusable() tells whether a
@@ -402,6 +424,12 @@ int frhip_margin_fwd_ex(float* logits, const int64_t* labels, int n, int c, cons
                         uint64_t* filtered, frhip_stream_t stream);
 int frhip_margin_bwd_ex(const float* gout, const int64_t* labels, const float* tsave, const uint64_t* filtered, int n, int c,
                         const frhip_margin_t* margin, float* gin, frhip_stream_t stream);
+/* per-row margins (frhip_margin_rows_t above; AdaFace.forward stand-alone).  NOT in place: out[n][c] = s x margin(logits), and the
+ * backward reads the caller's untouched logits to see where the clamp to [-1 + eps, 1 - eps] bound (gradient 0 there). */
+int frhip_margin_fwd_rows(const float* logits, const int64_t* labels, int n, int c, const frhip_margin_rows_t* margin, float* out,
+                          frhip_stream_t stream);
+int frhip_margin_bwd_rows(const float* gout, const float* logits, const int64_t* labels, int n, int c,
+                          const frhip_margin_rows_t* margin, float* gin, frhip_stream_t stream);
 int frhip_rows_max(const float* x, int n, int c, float* rowmax, frhip_stream_t stream);
 int frhip_rows_exp_sum(float* x, int n, int c, const float* rowmax, float* rowsum, frhip_stream_t stream);
 int frhip_rows_normalize(float* x, int n, int c, const float* rowsum, const int64_t* labels, float* ptarget,
