@@ -253,6 +253,173 @@ __global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __re
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Sub-centre variant (sub-center ArcFace, Deng et al., ECCV 2020): class c owns K centres, what[k * Nout + c] (plane-major: plane k is
+// a contiguous [Nout][D] table), and its cosine is the maximum over them.  The main loop runs once per plane against the same embedding
+// tile; a running element-wise maximum of the accumulators and the winning plane (2 bits per element, strict > when moving to a higher
+// plane: an exact tie stays with the lowest) are kept in registers, and the pooled tile enters the epilogue of head_kernel.  FWD and
+// the recompute do the same arithmetic on the same operands in the same order, so they pick the same winner bit for bit.
+//   FWD : additionally tsub[m] = winning plane of row m's target, -1 for a row whose label is -1.
+//   !FWD: d = d loss / d cos_c from the pooled cosine, once; then K tiles, plane k holding d where it won and an exact 0 elsewhere:
+//         dT[m][k * ldp + c] (ldp = the planes' column pitch, a whole number of 16-byte vectors; columns [Nout, ldp) of a plane zero),
+//         dTt[k * Nout + c][m].
+// A kernel of its own, epilogue and all, rather than a switch inside head_kernel: with one centre per class the library launches exactly
+// the kernels it launched before, arguments and instruction streams unchanged.
+constexpr int HEAD_SUB_MAX = 4;              // winners are packed 2 bits each: 16 elements of one nt column per 32-bit register
+
+template <typename T, bool FWD, int MK, bool FILT>
+__global__ __launch_bounds__(256, 2) void head_sub_kernel(NtGeom g, const void* __restrict__ ehat,
+                                                                 const void* __restrict__ what, const int* __restrict__ labels,
+                                                                 MarginArg<MK, FILT> mc, int K, float* __restrict__ part_max,
+                                                                 float* __restrict__ part_sum, float* __restrict__ ztarget,
+                                                                 int* __restrict__ tsub, const float* __restrict__ rowmax,
+                                                                 const float* __restrict__ rowsum, float gscale,
+                                                                 const float* __restrict__ upstream, void* __restrict__ dt, int ldt,
+                                                                 int ldp, void* __restrict__ dtt, int ldtt, int mtiles, int ntiles) {
+    typedef NtTile<T, 2, 2> Tile;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const uint32_t lin = xcd_remap(blockIdx.x, gridDim.x);
+    const int mtile = (int)(lin % (uint32_t)mtiles), ntile = (int)(lin / (uint32_t)mtiles);
+    NtMainloop<T, 2, 2> ml;
+    f32x4_t best[4][4];
+    uint32_t win[4] = {0u, 0u, 0u, 0u};                  // win[nt]: plane of element (mt, e) in bits 2 * (4 mt + e) ..
+    for (int k = 0; k < K; ++k) {
+        if (k) __syncthreads();                         // every wave is done reading the previous plane's operand stages
+        ml.run(g, ehat, reinterpret_cast<const char*>(what) + (size_t)k * g.b_bytes, smem, mtile, ntile, 0, g.ksteps);
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float v = ml.acc[nt][mt][e];
+                    if (k == 0) best[nt][mt][e] = v;
+                    else if (v > best[nt][mt][e]) {
+                        best[nt][mt][e] = v;
+                        win[nt] = (win[nt] & ~(3u << (2 * (4 * mt + e)))) | ((uint32_t)k << (2 * (4 * mt + e)));
+                    }
+                }
+    }
+
+    const int lane = lane_id(), wave = wave_id();
+    const int wm = wave >> 1, wn = wave & 1;
+    const int fi = lane & 15, fg = lane >> 4;
+    const int m0 = mtile * Tile::BM + wm * 64, n0 = ntile * Tile::BN + wn * 64;
+    const int group = ntile * 2 + wn;
+    if (!FWD && upstream) gscale *= upstream[0];
+
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+        const int m = m0 + mt * 16 + fi;
+        const bool mrow = m < g.M;
+        const int lab = mrow ? labels[m] : -1;
+        float gm = 0.f, gs = 1.f;
+        if (!FWD && mrow) { gm = rowmax[m]; gs = 1.f / rowsum[m]; }
+        [[maybe_unused]] float tlo, thi, m_ang = 0.f, m_add = 0.f;
+        if constexpr (MK == MG_ROWS) {
+            tlo = -1.f + mc.eps; thi = 1.f - mc.eps;
+            if (lab >= 0) { m_ang = mc.m_ang[m]; m_add = mc.m_add[m]; }
+        }
+        if (FWD && group == 0 && fg == 0 && mrow && lab < 0) tsub[m] = -1;
+        float z[4][4];
+        float vmax = -INFINITY;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int cls = n0 + nt * 16 + 4 * fg + e;
+                const float raw = best[nt][mt][e];
+                float t;
+                if constexpr (MK == MG_ROWS) t = fminf(fmaxf(raw, tlo), thi);
+                else t = fminf(fmaxf(raw, -1.f), 1.f);
+                float slope = 1.f;
+                bool filtered = false;
+                if (cls == lab) {
+                    if constexpr (MK == MG_ARC) {
+                        const float sin_t = sqrtf(1.f - t * t);
+                        if (t > mc.theta) { slope = mc.cos_m + t * mc.sin_m / sin_t; t = t * mc.cos_m - sin_t * mc.sin_m; }
+                        else t = t - mc.sinmm;
+                    } else if constexpr (MK == MG_ARC_EASY) {
+                        const float sin_t = sqrtf(1.f - t * t);
+                        if (t > 0.f) { slope = mc.cos_m + t * mc.sin_m / sin_t; t = t * mc.cos_m - sin_t * mc.sin_m; }
+                    } else if constexpr (MK == MG_ROWS) {
+                        t = rows_margin_target(t, m_ang, m_add, mc.eps, slope);
+                    } else {
+                        t = t - mc.m3;
+                    }
+                } else if constexpr (FILT) {
+                    if (t > mc.thr) { t = 0.f; filtered = true; }
+                }
+                const float zz = t * mc.s;
+                if (FWD) {
+                    z[nt][e] = (cls < g.Nout) ? zz : -INFINITY;          // the padded classes of the last tile never enter a sum
+                    vmax = fmaxf(vmax, z[nt][e]);
+                    if (cls == lab && mrow) { ztarget[m] = zz; tsub[m] = (int)((win[nt] >> (2 * (4 * mt + e))) & 3u); }
+                } else {
+                    float d = 0.f;
+                    if (cls < g.Nout && mrow) {
+                        const float p = __expf(zz - gm) * gs;
+                        bool inside;
+                        if constexpr (MK == MG_ROWS) inside = raw >= tlo && raw <= thi;
+                        else inside = raw >= -1.f && raw <= 1.f && !filtered;
+                        d = inside ? (p - (cls == lab ? 1.f : 0.f)) * gscale * mc.s * slope : 0.f;
+                    }
+                    best[nt][mt][e] = d;
+                }
+            }
+        if (FWD) {
+            vmax = lane_max_bit5(lane_max_bit4(vmax));
+            float vs = 0.f;
+            const float vref = vmax == -INFINITY ? 0.f : vmax;
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) vs += __expf(z[nt][e] - vref);
+            vs = lane_sum_bit5(lane_sum_bit4(vs));
+            if (fg == 0 && mrow) {
+                part_max[(size_t)group * g.M + m] = vmax;
+                part_sum[(size_t)group * g.M + m] = vs;
+            }
+        }
+    }
+    if (!FWD) {
+        constexpr int P = Tile::template stage_pitch<T>();
+        constexpr int EPV = 16 / (int)sizeof(T), LPR = 64 / EPV, RPI = 64 / LPR;
+        const int chunk = lane % LPR, rsub = lane / LPR;
+        const int n = n0 + chunk * EPV;
+        for (int k = 0; k < K; ++k) {
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        ml.acc[nt][mt][e] = ((win[nt] >> (2 * (4 * mt + e))) & 3u) == (uint32_t)k ? best[nt][mt][e] : 0.f;
+            const char* mine = ml.template stage_out<T>(smem);       // its leading barrier: the previous plane's tile has been read
+            T* o = reinterpret_cast<T*>(dt) + (size_t)k * ldp;
+            for (int it = 0; it < 64 / RPI; ++it) {
+                const int row = it * RPI + rsub, m = m0 + row;
+                if (m < g.M && n < ldp)         // columns [Nout, ldp) of the plane hold zeros
+                    *reinterpret_cast<Vec16<T>*>(o + (size_t)m * ldt + n) = *reinterpret_cast<const Vec16<T>*>(mine + row * P + chunk * 16);
+            }
+            if (dtt) {
+                T* ot = reinterpret_cast<T*>(dtt) + (size_t)k * g.Nout * ldtt;
+                const int cls = n0 + lane;
+                if (cls < g.Nout) {
+#pragma unroll
+                    for (int v = 0; v < 64 / EPV; ++v) {
+                        Vec16<T> tv;
+#pragma unroll
+                        for (int e = 0; e < EPV; ++e) tv.v[e] = *reinterpret_cast<const T*>(mine + (v * EPV + e) * P + lane * (int)sizeof(T));
+                        const int mcol = m0 + v * EPV;
+                        if (mcol < ldtt) *reinterpret_cast<Vec16<T>*>(ot + (size_t)cls * ldtt + mcol) = tv;
+                    }
+                }
+            }
+        }
+    }
+}
+
 // rowmax[m] = max_g part_max[g][m]; rowsum[m] = sum_g part_sum[g][m] * exp(part_max[g][m] - rowmax[m])
 // block = 16 rows x 16 group-lanes; each lane folds its share of the column groups with an online max/sum merge,
 // the 16 partial (max, sum) pairs of a row are merged through LDS.
@@ -386,6 +553,40 @@ static int head_launch(const NtGeom& g, const void* ehat, const void* what, cons
     return FRHIP_EINVAL;
 }
 
+// the sub-centre kernels: MC is MarginConstEx (descriptor margins; MarginArg cuts out what the variant takes) or MarginRows
+template <typename T, bool FWD, int MK, bool FILT, typename MC>
+static int head_sub_launch_mk(const NtGeom& g, const void* ehat, const void* what, const int* labels, const MC& mcx, int K,
+                              float* pmax, float* psum, float* zt, int* tsub, const float* rmax, const float* rsum, float gscale,
+                              const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt, hipStream_t stream) {
+    typedef NtTile<T, 2, 2> Tile;
+    const int mtiles = (g.M + Tile::BM - 1) / Tile::BM, ntiles = (g.Nout + Tile::BN - 1) / Tile::BN;
+    const int lds = Tile::template lds_bytes<T>();
+    const MarginArg<MK, FILT> mc = mcx;
+    auto kern = head_sub_kernel<T, FWD, MK, FILT>;
+    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "head_sub")) return FRHIP_ELAUNCH;
+    hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(256), lds, stream, g, ehat, what, labels, mc, K, pmax, psum,
+                       zt, tsub, rmax, rsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, mtiles, ntiles);
+    return check_launch("head_sub");
+}
+
+template <typename T, bool FWD>
+static int head_sub_launch(const NtGeom& g, const void* ehat, const void* what, const int* labels, const MarginConstEx& mc, int mk,
+                           bool filt, int K, float* pmax, float* psum, float* zt, int* tsub, const float* rmax, const float* rsum,
+                           float gscale, const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt, hipStream_t stream) {
+#define HEAD_VARIANT(MKV, FV) \
+    if (mk == MKV && filt == FV) \
+        return head_sub_launch_mk<T, FWD, MKV, FV>(g, ehat, what, labels, mc, K, pmax, psum, zt, tsub, rmax, rsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
+    HEAD_VARIANT(MG_ARC, false)
+    HEAD_VARIANT(MG_ARC, true)
+    HEAD_VARIANT(MG_ARC_EASY, false)
+    HEAD_VARIANT(MG_ARC_EASY, true)
+    HEAD_VARIANT(MG_COS, false)
+    HEAD_VARIANT(MG_COS, true)
+#undef HEAD_VARIANT
+    set_error("head_sub: unknown margin variant %d", mk);
+    return FRHIP_EINVAL;
+}
+
 static int head_geom(NtGeom& g, int dtype, int n, int cl, int d, const char* who) {
     const int es = dtype == FRHIP_DT_BF16 ? 2 : 4, bke = NT_ROWB / es;
     if ((dtype != FRHIP_DT_BF16 && dtype != FRHIP_DT_F32) || n <= 0 || cl <= 0 || d <= 0 || (d % bke)) {
@@ -516,6 +717,95 @@ extern "C" int frhip_head_bwd_dt_rows(int dtype, const void* ehat, const void* w
     if ((rc = margin_rows_desc(margin, mc, "frhip_head_bwd_dt_rows"))) return rc;
     if (dtype == FRHIP_DT_BF16) return head_launch_rows<bf16_t, false>(g, ehat, what, labels, mc, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
     return head_launch_rows<float, false>(g, ehat, what, labels, mc, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
+}
+
+// ---- K sub-centres per class.  `classes` is the number of classes; what holds K * classes rows, plane-major.
+static int head_sub_geom(NtGeom& g, int dtype, int n, int cl, int d, int K, const char* who) {
+    if (K < 1 || K > HEAD_SUB_MAX) { set_error("%s: %d sub-centres per class (1 .. %d are supported)", who, K, HEAD_SUB_MAX); return FRHIP_EINVAL; }
+    const int rc = head_geom(g, dtype, n, cl, d, who);
+    if (rc) return rc;
+    // the GEMMs behind the recompute kernel read all K planes as one table
+    if (1LL * K * cl * d * (dtype == FRHIP_DT_BF16 ? 2 : 4) > 0x7fffffffLL) {
+        set_error("%s: %d planes of %d classes exceed 2 GiB", who, K, cl);
+        return FRHIP_EINVAL;
+    }
+    return FRHIP_OK;
+}
+
+static int head_sub_pitches(int dtype, int n, int cl, int K, int ldt, int ldp, const void* dtt, int ldtt, const char* who) {
+    const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
+    if (ldp < cl || (ldp % epv) || 1LL * ldt < 1LL * K * ldp || (ldt % epv)) {
+        set_error("%s: bad dT pitches (row pitch %d, plane pitch %d, %d planes of %d classes)", who, ldt, ldp, K, cl);
+        return FRHIP_EINVAL;
+    }
+    if (dtt && (ldtt < n || (ldtt % epv))) { set_error("%s: bad transposed pitch %d", who, ldtt); return FRHIP_EINVAL; }
+    return FRHIP_OK;
+}
+
+extern "C" int frhip_head_sub_max(void) { return HEAD_SUB_MAX; }
+
+extern "C" int frhip_head_fwd_sub(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                                  int subcenters, const frhip_margin_t* margin, float* part_max, float* part_sum, float* ztarget,
+                                  int* tsub, float* rowmax, float* rowsum, hipStream_t stream) {
+    NtGeom g;
+    int rc = head_sub_geom(g, dtype, n, classes, d, subcenters, "frhip_head_fwd_sub");
+    if (rc) return rc;
+    MarginConstEx mc;
+    int mk;
+    bool filt;
+    if ((rc = margin_desc(margin, mc, mk, filt, "frhip_head_fwd_sub"))) return rc;
+    if (dtype == FRHIP_DT_BF16) rc = head_sub_launch<bf16_t, true>(g, ehat, what, labels, mc, mk, filt, subcenters, part_max, part_sum, ztarget, tsub, nullptr, nullptr, 0.f, nullptr, nullptr, 0, 0, nullptr, 0, stream);
+    else rc = head_sub_launch<float, true>(g, ehat, what, labels, mc, mk, filt, subcenters, part_max, part_sum, ztarget, tsub, nullptr, nullptr, 0.f, nullptr, nullptr, 0, 0, nullptr, 0, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(head_rowreduce_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, part_max, part_sum,
+                       frhip_head_groups(classes), n, rowmax, rowsum);
+    return check_launch("frhip_head_fwd_sub/rowreduce");
+}
+
+extern "C" int frhip_head_fwd_sub_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                                       int subcenters, const frhip_margin_rows_t* margin, float* part_max, float* part_sum,
+                                       float* ztarget, int* tsub, float* rowmax, float* rowsum, hipStream_t stream) {
+    NtGeom g;
+    int rc = head_sub_geom(g, dtype, n, classes, d, subcenters, "frhip_head_fwd_sub_rows");
+    if (rc) return rc;
+    MarginRows mc;
+    if ((rc = margin_rows_desc(margin, mc, "frhip_head_fwd_sub_rows"))) return rc;
+    if (dtype == FRHIP_DT_BF16) rc = head_sub_launch_mk<bf16_t, true, MG_ROWS, false>(g, ehat, what, labels, mc, subcenters, part_max, part_sum, ztarget, tsub, nullptr, nullptr, 0.f, nullptr, nullptr, 0, 0, nullptr, 0, stream);
+    else rc = head_sub_launch_mk<float, true, MG_ROWS, false>(g, ehat, what, labels, mc, subcenters, part_max, part_sum, ztarget, tsub, nullptr, nullptr, 0.f, nullptr, nullptr, 0, 0, nullptr, 0, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(head_rowreduce_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, part_max, part_sum,
+                       frhip_head_groups(classes), n, rowmax, rowsum);
+    return check_launch("frhip_head_fwd_sub_rows/rowreduce");
+}
+
+extern "C" int frhip_head_bwd_dt_sub(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                                     int subcenters, const frhip_margin_t* margin, const float* rowmax, const float* rowsum,
+                                     float gscale, const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt,
+                                     hipStream_t stream) {
+    NtGeom g;
+    int rc = head_sub_geom(g, dtype, n, classes, d, subcenters, "frhip_head_bwd_dt_sub");
+    if (rc) return rc;
+    if ((rc = head_sub_pitches(dtype, n, classes, subcenters, ldt, ldp, dtt, ldtt, "frhip_head_bwd_dt_sub"))) return rc;
+    MarginConstEx mc;
+    int mk;
+    bool filt;
+    if ((rc = margin_desc(margin, mc, mk, filt, "frhip_head_bwd_dt_sub"))) return rc;
+    if (dtype == FRHIP_DT_BF16) return head_sub_launch<bf16_t, false>(g, ehat, what, labels, mc, mk, filt, subcenters, nullptr, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
+    return head_sub_launch<float, false>(g, ehat, what, labels, mc, mk, filt, subcenters, nullptr, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
+}
+
+extern "C" int frhip_head_bwd_dt_sub_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                                          int subcenters, const frhip_margin_rows_t* margin, const float* rowmax, const float* rowsum,
+                                          float gscale, const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt,
+                                          hipStream_t stream) {
+    NtGeom g;
+    int rc = head_sub_geom(g, dtype, n, classes, d, subcenters, "frhip_head_bwd_dt_sub_rows");
+    if (rc) return rc;
+    if ((rc = head_sub_pitches(dtype, n, classes, subcenters, ldt, ldp, dtt, ldtt, "frhip_head_bwd_dt_sub_rows"))) return rc;
+    MarginRows mc;
+    if ((rc = margin_rows_desc(margin, mc, "frhip_head_bwd_dt_sub_rows"))) return rc;
+    if (dtype == FRHIP_DT_BF16) return head_sub_launch_mk<bf16_t, false, MG_ROWS, false>(g, ehat, what, labels, mc, subcenters, nullptr, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
+    return head_sub_launch_mk<float, false, MG_ROWS, false>(g, ehat, what, labels, mc, subcenters, nullptr, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
 }
 
 extern "C" int frhip_l2norm_rows(int dtype, const float* x, void* xhat, float* norms, int rows, int d, float eps,

@@ -801,9 +801,49 @@ def adaface_margins(norms, m, h, t_alpha, eps, batch_mean, batch_std, update):
     return out[0], out[1]
 
 
-def head_fwd(ehat, what, labels_i32, s, m, margin=None):
+def head_sub_max():
+    """the largest number of sub-centres per class the head kernels serve"""
+    return lib().frhip_head_sub_max()
+
+
+def _check_subcenters(what, subcenters):
+    k = int(subcenters)
+    if k < 1 or what.shape[0] % k:
+        raise ValueError("subcenters=%d: what must hold subcenters x classes rows, plane-major; it has %d" % (k, what.shape[0]))
+    return k
+
+
+def _head_fwd_sub(ehat, what, labels_i32, s, m, margin, k):
+    """head_fwd with k > 1 centres per class (frhip_head_fwd_sub / _sub_rows) -> (ztarget, rowmax, rowsum, tsub)"""
+    n, d = ehat.shape
+    classes = what.shape[0] // k
+    groups = lib().frhip_head_groups(classes)
+    dev = ehat.device
+    pm = torch.empty((groups, n), dtype=torch.float32, device=dev)
+    ps = torch.empty((groups, n), dtype=torch.float32, device=dev)
+    zt = torch.zeros((n,), dtype=torch.float32, device=dev)
+    tsub = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    rmax = torch.empty((n,), dtype=torch.float32, device=dev)
+    rsum = torch.empty((n,), dtype=torch.float32, device=dev)
+    if margin is not None and _is_rows(margin):
+        desc = _margin_rows_desc(margin, n)
+        check(lib().frhip_head_fwd_sub_rows(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, k, ctypes.byref(desc), _p(pm),
+                                            _p(ps), _p(zt), _p(tsub), _p(rmax), _p(rsum), _s()), "frhip_head_fwd_sub_rows")
+    else:
+        desc = _margin_desc((MARGIN_ARCFACE, 0, s, m, 0.0) if margin is None else margin)
+        check(lib().frhip_head_fwd_sub(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, k, ctypes.byref(desc), _p(pm),
+                                       _p(ps), _p(zt), _p(tsub), _p(rmax), _p(rsum), _s()), "frhip_head_fwd_sub")
+    return zt, rmax, rsum, tsub
+
+
+def head_fwd(ehat, what, labels_i32, s, m, margin=None, subcenters=1):
     """margin=None: ArcFace(s, m) (frhip_head_fwd); a (kind, easy, s, m, filter_thr) descriptor (frhip_head_fwd_ex); or per-row
-    margins (s, eps, m_ang, m_add), e.g. nets.ArcFace.RowMargins (frhip_head_fwd_rows)"""
+    margins (s, eps, m_ang, m_add), e.g. nets.ArcFace.RowMargins (frhip_head_fwd_rows).
+    subcenters = K > 1: what holds K x classes rows, plane-major (row k * classes + c); a class's cosine is the maximum over its K
+    centres and the result gains tsub [n] int32, the winning centre of each row's target (-1: no target on this shard)."""
+    k = _check_subcenters(what, subcenters)
+    if k > 1:
+        return _head_fwd_sub(ehat, what, labels_i32, s, m, margin, k)
     n, d = ehat.shape
     classes = what.shape[0]
     groups = lib().frhip_head_groups(classes)
@@ -860,9 +900,76 @@ def head_loss(q):
     return loss
 
 
-def head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, gscale, upstream=None, transposed=False, margin=None):
+_DT_TAIL = 256
+
+
+def _head_bwd_dt_sub(ehat, what, labels_i32, s, m, rmax, rsum, gscale, upstream, transposed, margin, k):
+    n, d = ehat.shape
+    classes = what.shape[0] // k
+    e = epv(ehat.dtype)
+    ldp = (classes + e - 1) // e * e
+    # head_dw_sub hands the TN GEMMs one plane at a time, as a pointer k * ldp columns into dT with dT's row pitch.  Those kernels fetch whole
+    # column tiles (up to 256 columns, bounded by the pitch only) and drop what lies past their class count at the output; in the last row
+    # of a later plane the tail of such a tile lies behind dT.  _DT_TAIL zeroed elements behind it keep those reads inside the allocation.
+    flat = torch.empty((n * k * ldp + _DT_TAIL,), dtype=ehat.dtype, device=ehat.device)
+    flat[n * k * ldp:].zero_()
+    dt = flat[:n * k * ldp].view(n, k, ldp)
+    dtt, ldtt = None, 0
+    if transposed:
+        ldtt = (n + e - 1) // e * e
+        dtt = torch.empty((k * classes, ldtt), dtype=ehat.dtype, device=ehat.device)
+    if margin is not None and _is_rows(margin):
+        desc = _margin_rows_desc(margin, n)
+        check(lib().frhip_head_bwd_dt_sub_rows(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, k, ctypes.byref(desc),
+                                               _p(rmax), _p(rsum), gscale, _p(upstream), _p(dt), k * ldp, ldp, _p(dtt), ldtt, _s()),
+              "frhip_head_bwd_dt_sub_rows")
+    else:
+        desc = _margin_desc((MARGIN_ARCFACE, 0, s, m, 0.0) if margin is None else margin)
+        check(lib().frhip_head_bwd_dt_sub(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, k, ctypes.byref(desc),
+                                          _p(rmax), _p(rsum), gscale, _p(upstream), _p(dt), k * ldp, ldp, _p(dtt), ldtt, _s()),
+              "frhip_head_bwd_dt_sub")
+    return (dt, dtt) if transposed else dt
+
+
+def head_dw_sub(dt, ehat, what, wnorm, out_scale=1.0):
+    """class-centre gradient [K x classes, d] fp32 from the K-plane dT [n, K, plane pitch] that head_bwd_dt(subcenters=K) returned (its
+    allocation carries the tail the per-plane reads need: pass that tensor, not a copy): the kernels
+    behind head_dw / gemm_tn + l2norm_bwd, once per plane, each on its plane's columns of dT (row pitch K x plane pitch) and its
+    [classes, d] rows of the table"""
+    n, k, ldp = dt.shape
+    d = ehat.shape[1]
+    classes = what.shape[0] // k
+    dtype = dt_of(ehat)
+    fused = bool(lib().frhip_head_dw_ok(dtype, n, classes, d))
+    dw = torch.empty((k * classes, d), dtype=torch.float32, device=ehat.device)
+    ws = None if fused else workspace(ehat.device)
+    assert dt.is_cuda and dt.is_contiguous()
+    behind = dt.untyped_storage().nbytes() - (dt.storage_offset() + dt.numel()) * dt.element_size()
+    if behind < _DT_TAIL * dt.element_size():
+        raise ValueError("head_dw_sub: dT must be the tensor head_bwd_dt(subcenters=K) returned: the per-plane reads need the %d zeroed "
+                         "elements its allocation carries behind it" % _DT_TAIL)
+    for j in range(k):
+        rows = slice(j * classes, (j + 1) * classes)
+        plane = dt.data_ptr() + j * ldp * dt.element_size()          # dT[:, j, :]: same row pitch, whole 16-byte vectors in
+        if fused:
+            check(lib().frhip_head_dw(dtype, plane, k * ldp, _p(ehat), _p(what[rows]), _p(wnorm[rows]), _p(dw[rows]), n, classes, d,
+                                      out_scale, _s()), "frhip_head_dw")
+        else:
+            check(lib().frhip_gemm_tn_overwrite(dtype, plane, _p(ehat), _p(dw[rows]), n, classes, k * ldp, d, _p(ws),
+                                                ws.numel() * 4, _s()), "frhip_gemm_tn_overwrite")
+    if fused:
+        return dw
+    return l2norm_bwd(dw, what, wnorm, out_scale=out_scale)
+
+
+def head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, gscale, upstream=None, transposed=False, margin=None, subcenters=1):
     """dT [n][classes padded]; transposed=True: also dTt [classes][n padded] from the same launch -> (dT, dTt).
-    margin: as in head_fwd"""
+    margin: as in head_fwd.
+    subcenters = K > 1 (what: K x classes rows, plane-major): dT is [n][K][classes padded] -- plane k holds d loss / d cos where centre k
+    won its (row, class) and an exact 0 elsewhere, pad columns 0 -- and dTt is [K x classes][n padded], row k * classes + c."""
+    k = _check_subcenters(what, subcenters)
+    if k > 1:
+        return _head_bwd_dt_sub(ehat, what, labels_i32, s, m, rmax, rsum, gscale, upstream, transposed, margin, k)
     n, d = ehat.shape
     classes = what.shape[0]
     e = epv(ehat.dtype)

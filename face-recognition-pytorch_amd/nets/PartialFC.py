@@ -21,6 +21,9 @@ What runs where
     reduce-scatter of dE issued before the dW GEMM so the two overlap (the reference loops world_size reduce() calls,
     :510-519).  AdaFace alone adds a fifth, small one: an all-gather of the rows' norms ([N] floats), from which every rank derives the
     same per-row margins and the same running statistics (frhip_adaface_margins, one launch).
+`conf.subcenters = K` (not in the reference; sub-center ArcFace): every class owns K centres, the table is plane-major [K x num_local, D]
+(centre k of class c in row k * num_local + c), the fused kernels take the maximum over a class's centres on their accumulators and send
+its gradient to the winner alone; sampling, sharding and the collectives stay at class level.  Absent or 1: the calls made before.
 The floating-point steps sit behind `HipHeadKernels`; tests on CPU/gloo swap in an oracle-backed double to
 exercise the distributed host logic without a GPU.  There is no built-in CPU fallback.
 """
@@ -53,8 +56,11 @@ class HipHeadKernels:
     def normalize(self, x):
         return self.ops.l2norm_rows(x.contiguous(), self.dtype)          # (xhat, norms)
 
-    def forward_stats(self, ehat, what, labels_i32, s, m, margin=None):
-        """margin: None = ArcFace(s, m); else a nets.ArcFace.Margin (CosFace, easy margin, interclass filtering) or RowMargins (AdaFace)"""
+    def forward_stats(self, ehat, what, labels_i32, s, m, margin=None, subcenters=1):
+        """margin: None = ArcFace(s, m); else a nets.ArcFace.Margin (CosFace, easy margin, interclass filtering) or RowMargins (AdaFace).
+        subcenters = K > 1: what holds K x classes rows, plane-major, and the result gains tsub (the winning centre of every row's target)"""
+        if subcenters > 1:
+            return self.ops.head_fwd(ehat, what, labels_i32, s, m, margin=margin, subcenters=subcenters)
         return self.ops.head_fwd(ehat, what, labels_i32, s, m, margin=margin)     # (ztarget, rowmax, rowsum) of this shard
 
     def adaface_margins(self, norms, mg, batch_mean, batch_std, update):
@@ -77,12 +83,23 @@ class HipHeadKernels:
         return self.ops.head_merge_stats(gathered)                         # global (rowmax, rowsum, q)
 
     def backward(self, ehat, enorm, what, wnorm, labels_i32, s, m, rmax, rsum, n_global, upstream, e_scale=1.0, on_de=None,
-                 margin=None):
-        """-> (d_emb * e_scale, d_weight).  margin: as in forward_stats.  on_de(d_emb) is called as soon as the embedding gradient is enqueued, before the
+                 margin=None, subcenters=1):
+        """-> (d_emb * e_scale, d_weight).  margin, subcenters: as in forward_stats.  on_de(d_emb) is called as soon as the embedding gradient is enqueued, before the
         weight-gradient GEMM: the caller starts the cross-rank reduce-scatter there and the two overlap."""
         ops = self.ops
         n, d = ehat.shape
         classes = what.shape[0]
+        if subcenters > 1:
+            # the recompute kernel writes the gradient of a (row, class) into the winning centre's plane and exact zeros into the others: the
+            # GEMMs below then serve K x classes rows as they are (dE: one call over all planes; dW: plane by plane, ops.head_dw_sub)
+            dt, dtt = ops.head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, 1.0 / n_global, upstream, transposed=True, margin=margin,
+                                      subcenters=subcenters)
+            d_eh = torch.zeros((n, d), dtype=torch.float32, device=ehat.device)
+            ops.gemm_tn(dtt, what, d_eh, kc=n)
+            d_e = ops.l2norm_bwd(d_eh, ehat, enorm, out_scale=e_scale)
+            if on_de is not None:
+                on_de(d_e)
+            return d_e, ops.head_dw_sub(dt, ehat, what, wnorm)
         # dT and its transpose from ONE launch (the embedding gradient contracts over classes, the weight gradient over samples)
         dt, dtt = ops.head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, 1.0 / n_global, upstream, transposed=True, margin=margin)
         d_eh = torch.zeros((n, d), dtype=torch.float32, device=ehat.device)
@@ -168,9 +185,12 @@ class _MarginSoftmaxFn(torch.autograd.Function):
     Arithmetic: SURVEY.md Appendix A steps 1-7 (nets/PartialFC.py:182, :198-207, nets/ArcFace.py:76-91, :441-484, :504-522)."""
 
     @staticmethod
-    def forward(ctx, local_embeddings, weight_activated, labels_i32, kern, s, m, world_size, collectives, margin=None, adaface=None):
+    def forward(ctx, local_embeddings, weight_activated, labels_i32, kern, s, m, world_size, collectives, margin=None, adaface=None,
+                subcenters=1, sub_out=None):
         """adaface: None, or (AdaFace module, this rank's norms [rows]) -- the per-row margins are then derived here, from the norms of
-        the global batch in rank order, and `margin` is ignored"""
+        the global batch in rank order, and `margin` is ignored.
+        subcenters = K > 1: weight_activated holds K x classes rows, plane-major; the winning centre of every row's target (int32 [N], -1
+        where another shard owns the row) is appended to the list sub_out"""
         local_embeddings = local_embeddings.contiguous()
         rows, dim = local_embeddings.shape
         if collectives:                                                         # :182 (C1)
@@ -189,7 +209,12 @@ class _MarginSoftmaxFn(torch.autograd.Function):
             rm = module.row_margins(norms, kern)            # ONE launch; advances the running buffers in training mode
             extra, row_vecs = {"margin": rm}, (rm.m_ang, rm.m_add)
             ctx.row_consts = (rm.s, rm.eps)
-        zt, rmax, rsum = kern.forward_stats(ehat, what, labels_i32, s, m, **extra)
+        if subcenters > 1:                                   # one centre per class: the calls made before sub-centres existed
+            zt, rmax, rsum, tsub = kern.forward_stats(ehat, what, labels_i32, s, m, subcenters=subcenters, **extra)
+            if sub_out is not None:
+                sub_out.append(tsub)
+        else:
+            zt, rmax, rsum = kern.forward_stats(ehat, what, labels_i32, s, m, **extra)
         if collectives:                                                         # :448, :453, :459 (C3-C5) in one exchange
             mine = kern.pack_stats(zt, labels_i32, rmax, rsum)
             allst = _all_gather_flat(mine.new_empty((world_size * mine.shape[0], mine.shape[1])), mine)
@@ -199,17 +224,18 @@ class _MarginSoftmaxFn(torch.autograd.Function):
         loss = kern.loss(q)
         ctx.kern, ctx.s, ctx.m, ctx.world_size, ctx.collectives, ctx.rows = kern, s, m, world_size, collectives, rows
         ctx.extra = {} if row_vecs else extra
+        ctx.sub = {"subcenters": subcenters} if subcenters > 1 else {}
         ctx.save_for_backward(ehat, enorm, what, wnorm, labels_i32, rmax, rsum, *row_vecs)
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, grad_loss):
         ehat, enorm, what, wnorm, labels_i32, rmax, rsum, *row_vecs = ctx.saved_tensors
-        extra = {"margin": RowMargins(*ctx.row_consts, *row_vecs)} if row_vecs else ctx.extra
+        extra = dict({"margin": RowMargins(*ctx.row_consts, *row_vecs)} if row_vecs else ctx.extra, **ctx.sub)
         up = grad_loss.reshape(1).float().contiguous()
         if not ctx.collectives:
             d_e, d_w = ctx.kern.backward(ehat, enorm, what, wnorm, labels_i32, ctx.s, ctx.m, rmax, rsum, ehat.shape[0], up, **extra)
-            return d_e, d_w, None, None, None, None, None, None, None, None
+            return d_e, d_w, None, None, None, None, None, None, None, None, None, None
         # :504-522 (C6): reduce-scatter(SUM) of dE, x world_size (folded into the normalise-backward's scale); issued as soon
         # as dE is enqueued so that it runs beside the dW GEMM
         pending = []
@@ -223,7 +249,7 @@ class _MarginSoftmaxFn(torch.autograd.Function):
         d_local, work = pending[0]
         if work is not None:
             work.wait()
-        return d_local, d_w, None, None, None, None, None, None, None, None
+        return d_local, d_w, None, None, None, None, None, None, None, None, None, None
 
 
 class DistCrossEntropyFunc(torch.autograd.Function):
@@ -284,7 +310,17 @@ class _PartialFCBase(torch.nn.Module):
         self.is_updated: bool = True
         self.init_weight_update: bool = True
         self._state_names = self._optimizer_state_names()
-        init = torch.normal(0, 0.01, (self.num_local, self.embedding_size))
+        # sub-center ArcFace (Deng et al., ECCV 2020): K centres per class, a class's cosine is the maximum over them.  The table is
+        # plane-major, [K x num_local, D] with centre k of class c in row k * num_local + c: plane k is a [num_local, D] table like today's
+        self.subcenters: int = int(getattr(conf, "subcenters", 1) or 1)
+        if self.subcenters < 1:
+            raise ValueError("conf.subcenters must be >= 1, got %r" % (getattr(conf, "subcenters"),))
+        self.last_target_sub = None            # K > 1: the winning centre of every row's target in the last forward (int32 [N], -1: not ours)
+        if getattr(conf, "subcenter_track", False):
+            self.register_buffer("sub_hits", torch.zeros(self.subcenters, self.num_local, dtype=torch.int64))
+        else:
+            self.sub_hits = None
+        init = torch.normal(0, 0.01, (self.subcenters * self.num_local, self.embedding_size))
         if self.sample_rate < 1:
             self.register_buffer("weight", tensor=init)
             for nm in self._state_names:
@@ -356,10 +392,23 @@ class _PartialFCBase(torch.nn.Module):
         """rows `index` of the shard become this step's parameter (reference :120-129)"""
         self.weight_index = index
         k = self.kernels
-        self.weight_activated = torch.nn.Parameter(k.gather_rows(self.weight, index))
+        rows = self._plane_rows(index)
+        self.weight_activated = torch.nn.Parameter(k.gather_rows(self.weight, rows))
         for nm in self._state_names:
-            setattr(self, "weight_activated_" + nm, k.gather_rows(getattr(self, "weight_" + nm), index))
+            setattr(self, "weight_activated_" + nm, k.gather_rows(getattr(self, "weight_" + nm), rows))
         self._install_optimizer_state(optimizer)
+
+    def _plane_rows(self, index):
+        """rows of the full [K x num_local, D] tables that the sampled classes `index` own: index + k * num_local, plane after plane, so
+        the activated table is [K x num_sample, D] and plane-major as well.  K = 1: `index` itself."""
+        if self.subcenters == 1:
+            return index
+        cached = getattr(self, "_plane_rows_of", None)
+        if cached is not None and cached[0] is index:
+            return cached[1]
+        rows = torch.cat([index + k * self.num_local for k in range(self.subcenters)])
+        self._plane_rows_of = (index, rows)
+        return rows
 
     def _sample_kernel_ok(self, dev):
         """one launch of frhip_pfc_sample (csrc/pfc_sample.hip) instead of the ~25 torch launches of the label side"""
@@ -480,9 +529,10 @@ class _PartialFCBase(torch.nn.Module):
             return
         if self.sample_rate < 1:
             k = self.kernels
-            k.scatter_rows(self.weight_activated.data, self.weight_index, self.weight)
+            rows = self._plane_rows(self.weight_index)
+            k.scatter_rows(self.weight_activated.data, rows, self.weight)
             for nm in self._state_names:
-                k.scatter_rows(getattr(self, "weight_activated_" + nm), self.weight_index, getattr(self, "weight_" + nm))
+                k.scatter_rows(getattr(self, "weight_activated_" + nm), rows, getattr(self, "weight_" + nm))
 
     def forward(self, local_embeddings, local_labels, optimizer, norms=None):
         """norms: this rank's [B] embedding norms BEFORE normalisation, for a margin that derives per-row margins from them (AdaFace,
@@ -537,8 +587,7 @@ class _PartialFCBase(torch.nn.Module):
         # it made before per-row margins existed
         tail = (None, (self.margin_softmax, norms)) if isinstance(mg, AdaMargin) else (margin,)
         if ready is not None and ready.numel() == n_global:      # everything label-side was done by prepare()
-            return _MarginSoftmaxFn.apply(local_embeddings, self.weight_activated, ready, self.kernels, s, m,
-                                          self.world_size, collectives, *tail)
+            return self._margin_softmax(local_embeddings, ready, s, m, collectives, tail)
         n_pos = None
         if prep is not None and prep[1].numel() == n_global:
             labels, n_pos = prep[1], prep[2]                      # gathered at the start of the step by prepare()
@@ -553,8 +602,47 @@ class _PartialFCBase(torch.nn.Module):
         labels = torch.where(index_positive, labels - self.class_start, torch.full_like(labels, -1))
         if self.sample_rate < 1:
             self.sample(labels, index_positive, optimizer, n_pos)
-        return _MarginSoftmaxFn.apply(local_embeddings, self.weight_activated, labels.view(-1).to(torch.int32).contiguous(),
-                                      self.kernels, s, m, self.world_size, collectives, *tail)
+        return self._margin_softmax(local_embeddings, labels.view(-1).to(torch.int32).contiguous(), s, m, collectives, tail)
+
+    def _margin_softmax(self, local_embeddings, labels_i32, s, m, collectives, tail):
+        if self.subcenters == 1:
+            return _MarginSoftmaxFn.apply(local_embeddings, self.weight_activated, labels_i32, self.kernels, s, m,
+                                          self.world_size, collectives, *tail)
+        won = []
+        loss = _MarginSoftmaxFn.apply(local_embeddings, self.weight_activated, labels_i32, self.kernels, s, m,
+                                      self.world_size, collectives, *(tail + (None,))[:2], self.subcenters, won)
+        self.last_target_sub = won[0]
+        if self.sub_hits is not None and self.training:
+            self._count_sub_hits(labels_i32, won[0])
+        return loss
+
+    @torch.no_grad()
+    def _count_sub_hits(self, labels_i32, tsub):
+        """sub_hits[winning centre][class] += 1 for every row whose target this shard owns; the class is the row of the FULL shard table
+        (through weight_index when sampling).  Plain indexing, no host synchronisation."""
+        owned = tsub >= 0
+        pos = labels_i32.long().clamp(min=0)
+        cls = self.weight_index[pos] if self.sample_rate < 1 else pos
+        self.sub_hits.view(-1).index_add_(0, tsub.long().clamp(min=0) * self.num_local + cls, owned.long())
+
+    def dominant_subcenters(self):
+        """[num_local] int64: the centre of every class that won its targets most often (sub_hits, conf.subcenter_track), the lowest
+        such centre on a tie -- also for a class that was never a target"""
+        if self.sub_hits is None:
+            raise RuntimeError("dominant_subcenters() needs the sub_hits counts: build the head with conf.subcenter_track = True")
+        k = torch.arange(self.subcenters, device=self.sub_hits.device).view(-1, 1).expand_as(self.sub_hits)
+        top = self.sub_hits.max(dim=0, keepdim=True).values
+        return torch.where(self.sub_hits == top, k, torch.full_like(k, self.subcenters)).min(dim=0).values
+
+    @torch.no_grad()
+    def collapse_subcenters(self):
+        """[num_local, D]: the dominant centre of every class, the starting table of the paper's second stage -- it loads into a head
+        built with one centre per class through load_state_dict({"weight": ...}).  With sampling, call update() first if a step is
+        still pending in weight_activated."""
+        table = (self.weight if self.sample_rate < 1 else self.weight_activated.data).detach()
+        dom = self.dominant_subcenters().to(table.device)
+        planes = table.view(self.subcenters, self.num_local, -1)
+        return planes[dom, torch.arange(self.num_local, device=table.device)].clone()
 
     def arm_early_update(self, optimizer):
         """Call between forward() and loss.backward() of a step whose gradient clip leaves the class centres out and that calls
@@ -595,6 +683,8 @@ class _PartialFCBase(torch.nn.Module):
             if module is not None:
                 module.state_dict(destination=destination, prefix=prefix + name + ".", keep_vars=keep_vars)
         destination["weight"] = (self.weight if self.sample_rate < 1 else self.weight_activated.data).detach()
+        if self.sub_hits is not None:
+            destination["sub_hits"] = self.sub_hits.detach()
         return destination
 
     def load_state_dict(self, state_dict, strict: bool = True):
@@ -605,6 +695,15 @@ class _PartialFCBase(torch.nn.Module):
                 buf, src = getattr(self.margin_softmax, name), state_dict.get("margin_softmax." + name)
                 with torch.no_grad():
                     buf.copy_(src.to(buf.device).reshape(buf.shape)) if src is not None else buf.fill_(init)
+        rows = self.subcenters * self.num_local
+        if state_dict["weight"].dim() != 2 or state_dict["weight"].shape[0] != rows:
+            raise ValueError("load_state_dict: this head holds %d sub-centre(s) x %d classes = %d rows (plane-major: row k * %d + c), "
+                             "the checkpoint's weight is %s" % (self.subcenters, self.num_local, rows, self.num_local,
+                                                                tuple(state_dict["weight"].shape)))
+        if self.sub_hits is not None:           # a checkpoint written without the counts: they start again from zero
+            src = state_dict.get("sub_hits")
+            with torch.no_grad():
+                self.sub_hits.copy_(src.to(self.sub_hits.device)) if src is not None else self.sub_hits.zero_()
         if self.sample_rate < 1:
             self.weight = state_dict["weight"].to(self.weight.device)
             for nm in self._state_names:

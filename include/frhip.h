@@ -336,6 +336,35 @@ int frhip_head_bwd_dt_rows(int dtype, const void* ehat, const void* what, const 
                            int d, const frhip_margin_rows_t* margin, const float* rowmax, const float* rowsum, float gscale,
                            const float* upstream, void* dt, int ldt, void* dtt, int ldtt, frhip_stream_t stream);
 
+/* K sub-centres per class (not in the reference: sub-center ArcFace, Deng et al., ECCV 2020).  what holds subcenters x classes rows,
+ * plane-major: centre k of class c is row k * classes + c, each normalised on its own.  The cosine of (row, class) is the maximum over the
+ * class's centres, an exact tie going to the lowest k; clamp, margin, filtering, x s and the row statistics then see that cosine exactly
+ * as the entry points above see theirs.  `classes`, labels, part_max / part_sum (frhip_head_groups(classes) rows) and the row vectors are
+ * those of one plane.
+ *   forward : tsub[n] (int32) = the winning centre of the row's target, -1 where the label is -1.
+ *   backward: d loss / d cos goes to the winning centre alone, the other centres of that (row, class) get an exact 0.  The same operands
+ *             go through the same arithmetic as in the forward kernel, so the winners are the same bit for bit.
+ *             dt[m][k * ldp + c]: ldp >= classes is the planes' column pitch and a multiple of the 16-byte vector (so classes need not be),
+ *             ldt >= subcenters * ldp the row pitch; columns [classes, ldp) of every plane are written as zeros.
+ *             dtt (may be NULL) [subcenters * classes][ldtt], row k * classes + c.
+ * frhip_head_sub_max(): the largest subcenters served.  subcenters outside 1 .. that, a plane or the whole table beyond 2 GiB, or a bad
+ * pitch: FRHIP_EINVAL, nothing is launched. */
+int frhip_head_sub_max(void);
+int frhip_head_fwd_sub(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                       int subcenters, const frhip_margin_t* margin, float* part_max, float* part_sum, float* ztarget,
+                       int* tsub, float* rowmax, float* rowsum, frhip_stream_t stream);
+int frhip_head_fwd_sub_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                            int subcenters, const frhip_margin_rows_t* margin, float* part_max, float* part_sum,
+                            float* ztarget, int* tsub, float* rowmax, float* rowsum, frhip_stream_t stream);
+int frhip_head_bwd_dt_sub(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                          int subcenters, const frhip_margin_t* margin, const float* rowmax, const float* rowsum,
+                          float gscale, const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt,
+                          frhip_stream_t stream);
+int frhip_head_bwd_dt_sub_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                               int subcenters, const frhip_margin_rows_t* margin, const float* rowmax, const float* rowsum,
+                               float gscale, const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt,
+                               frhip_stream_t stream);
+
 /* ---- bn1 -> relu -> conv2 of a BasicBlock (nets/resnet.py:91-93) WITHOUT the activated tensor: the BatchNorm-apply + ReLU
  * is folded into the operand path of the convolution (forward) and of its weight gradient, which read the saved BatchNorm
  * INPUT x and form relu(x * in_scale[c] + in_shift[c]) in LDS.  bf16, 3x3 / stride 1 / pad 1; *_fusable() tells whether a
