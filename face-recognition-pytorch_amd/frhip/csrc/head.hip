@@ -8,15 +8,14 @@
 //   nets/PartialFC.py:441-484 DistCrossEntropyFunc forward/backward.
 // Cross-rank steps (all-reduce MAX / SUM of the per-row scalars) are done by the host between these kernels.
 // The other margin modules of the reference (nets/ArcFace.py:5-61 CombinedMarginLoss with interclass filtering and easy_margin,
-// :94-106 CosFace) are compile-time variants of the same epilogue (template arguments MK, FILT of head_kernel), and so is the per-row
+// :94-106 CosFace) are compile-time variants of the same epilogue (template arguments MK, FILT of head_epilogue), and so is the per-row
 // margin (MG_ROWS: AdaFace, not in the reference), whose two margins per row come from adaface_margins_kernel below.
 #include "igemm_nt.h"
-#include "margin_rows.h"
+#include "margin_shared.h"
 #include "frhip.h"
 
 namespace frhip {
 
-struct MarginConst { float s, cos_m, sin_m, theta, sinmm; };
 struct MarginConstEx : MarginConst { float m3, thr; };       // CosFace margin, interclass-filtering threshold
 
 // margin variants of the head epilogue.  The ArcFace kernel (the reference default, bench.py) keeps the plain MarginConst
@@ -116,38 +115,26 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The epilogue of both head kernels, on one wave's 64 x 64 tile of cosines acc[nt][mt] (rows from m0, classes from n0).
 // FWD = true : partial row max / sum-exp per 64-class column group, target logit.
-// FWD = false: dT tile (compute dtype) from the recomputed cosines and the global row max / sum.
+// FWD = false: acc becomes d(loss)/d(cos), from the recomputed cosines and the global row max / sum; 0 in rows past M and classes past Nout.
 // MK: MG_ARC (cos(theta + m), below cos(pi - m) t - m sin(pi - m)), MG_ARC_EASY (cos(theta + m) for t > 0, else t), MG_COS (t - m3),
 // MG_ROWS (row m: every cosine clamped to [-1 + eps, 1 - eps], target cos(clamp(theta + m_ang[m], eps, pi - eps)) - m_add[m], slope 0 where
 // a clamp binds; frhip_margin_rows_t in frhip.h).
 // FILT: interclass filtering (reference nets/ArcFace.py:28-39): an element that is not its row's target and whose clamped cosine is
 // > thr is multiplied by 0 -- logit 0, which still counts in the softmax sum, and d/dcos 0 (the reference builds the mask under
 // no_grad); a row without a target on this shard (label -1) is filtered in every column.
-template <typename T, bool FWD, int MK, bool FILT>
-__global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __restrict__ ehat,
-                                                             const void* __restrict__ what, const int* __restrict__ labels,
-                                                             MarginArg<MK, FILT> mc, float* __restrict__ part_max,
-                                                             float* __restrict__ part_sum, float* __restrict__ ztarget,
-                                                             const float* __restrict__ rowmax, const float* __restrict__ rowsum,
-                                                             float gscale, const float* __restrict__ upstream,
-                                                             void* __restrict__ dt, int ldt, void* __restrict__ dtt, int ldtt,
-                                                             int mtiles, int ntiles) {
-    typedef NtTile<T, 2, 2> Tile;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const uint32_t lin = xcd_remap(blockIdx.x, gridDim.x);
-    // mtile fastest: the (few) row tiles that share one weight tile run together on one XCD
-    const int mtile = (int)(lin % (uint32_t)mtiles), ntile = (int)(lin / (uint32_t)mtiles);
-    NtMainloop<T, 2, 2> ml;
-    ml.run(g, ehat, what, smem, mtile, ntile, 0, g.ksteps);
-
-    const int lane = lane_id(), wave = wave_id();
-    const int wm = wave >> 1, wn = wave & 1;
+// SUB (head_sub_kernel; win is not read otherwise): win[nt] holds the winning plane of element (mt, e) in bits 2 * (4 mt + e) .., and FWD
+// writes tsub[m] = the winning plane of row m's target, -1 for a row whose label is -1.
+// lane = lane_id(), from the kernel.  The margin goes by value and the pointers carry no __restrict__ (the kernels' own parameters do): with it
+// the compiler emits other floating-point compares and selects in some instantiations than it did when this text stood in the kernels.
+template <bool FWD, int MK, bool FILT, bool SUB>
+__device__ __forceinline__ void head_epilogue(int lane, const NtGeom& g, f32x4_t (&acc)[4][4], const uint32_t* win, int m0, int n0,
+                                              int group, const int* labels, MarginArg<MK, FILT> mc, float* part_max, float* part_sum,
+                                              float* ztarget, int* tsub, const float* rowmax, const float* rowsum, float gscale,
+                                              const float* upstream) {
     const int fi = lane & 15, fg = lane >> 4;
-    const int m0 = mtile * Tile::BM + wm * 64, n0 = ntile * Tile::BN + wn * 64;
-    const int group = ntile * 2 + wn;                   // 64-class column group id
     if (!FWD && upstream) gscale *= upstream[0];        // d(loss)/d(loss) stays on the device: no host sync
-
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
         const int m = m0 + mt * 16 + fi;
@@ -160,6 +147,8 @@ __global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __re
             tlo = -1.f + mc.eps; thi = 1.f - mc.eps;
             if (lab >= 0) { m_ang = mc.m_ang[m]; m_add = mc.m_add[m]; }       // lab >= 0 implies m < M
         }
+        if constexpr (SUB)
+            if (FWD && group == 0 && fg == 0 && mrow && lab < 0) tsub[m] = -1;
         float z[4][4];
         float vmax = -INFINITY;
 #pragma unroll
@@ -167,7 +156,7 @@ __global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __re
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int cls = n0 + nt * 16 + 4 * fg + e;
-                const float raw = ml.acc[nt][mt][e];
+                const float raw = acc[nt][mt][e];
                 float t;
                 if constexpr (MK == MG_ROWS) t = fminf(fmaxf(raw, tlo), thi);
                 else t = fminf(fmaxf(raw, -1.f), 1.f);
@@ -191,9 +180,12 @@ __global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __re
                 }
                 const float zz = t * mc.s;
                 if (FWD) {
-                    z[nt][e] = (cls < g.Nout) ? zz : -INFINITY;
+                    z[nt][e] = (cls < g.Nout) ? zz : -INFINITY;          // the padded classes of the last tile never enter a sum
                     vmax = fmaxf(vmax, z[nt][e]);
-                    if (cls == lab && mrow) ztarget[m] = zz;
+                    if (cls == lab && mrow) {
+                        ztarget[m] = zz;
+                        if constexpr (SUB) tsub[m] = (int)((win[nt] >> (2 * (4 * mt + e))) & 3u);
+                    }
                 } else {
                     float d = 0.f;
                     if (cls < g.Nout && mrow) {
@@ -203,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __re
                         else inside = raw >= -1.f && raw <= 1.f && !filtered;
                         d = inside ? (p - (cls == lab ? 1.f : 0.f)) * gscale * mc.s * slope : 0.f;
                     }
-                    ml.acc[nt][mt][e] = d;
+                    acc[nt][mt][e] = d;
                 }
             }
         if (FWD) {
@@ -221,50 +213,81 @@ __global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __re
             }
         }
     }
-    if (!FWD) {
-        constexpr int P = Tile::template stage_pitch<T>();
-        constexpr int EPV = 16 / (int)sizeof(T), LPR = 64 / EPV, RPI = 64 / LPR;
-        const char* mine = ml.template stage_out<T>(smem);
-        const int chunk = lane % LPR, rsub = lane / LPR;
-        const int n = n0 + chunk * EPV;
-        T* o = reinterpret_cast<T*>(dt);
-        for (int it = 0; it < 64 / RPI; ++it) {
-            const int row = it * RPI + rsub, m = m0 + row;
-            if (m < g.M && n < ldt)         // columns in [Nout, ldt) hold zeros (dT pitch padding)
-                *reinterpret_cast<Vec16<T>*>(o + (size_t)m * ldt + n) = *reinterpret_cast<const Vec16<T>*>(mine + row * P + chunk * 16);
-        }
-        if (dtt) {
-            // the same tile transposed, dTt[class][sample] (pitch ldtt, multiple of the 16-byte vector): the embedding-gradient GEMM
-            // contracts over classes and wants class-major rows -- written here, a separate transpose pass (125 MB read + written at
-            // 122 000 classes) is not needed.  Lane = class row of the tile, eight 16-byte vectors of samples each.
-            T* ot = reinterpret_cast<T*>(dtt);
-            const int cls = n0 + lane;
-            if (cls < g.Nout) {
+}
+
+// One wave's tile ml.acc through LDS to o[m][n] (row pitch ldt, columns below ncols) and, with ot set, transposed to ot[class][sample].
+// stage_out begins with a barrier: whatever read the LDS before (the operand stages, the previous plane's tile) is done.
+template <typename T>
+__device__ __forceinline__ void head_store_tile(const NtGeom& g, NtMainloop<T, 2, 2>& ml, char* smem, int m0, int n0, T* o, int ldt,
+                                                int ncols, T* ot, int ldtt) {
+    constexpr int P = NtTile<T, 2, 2>::template stage_pitch<T>();
+    constexpr int EPV = 16 / (int)sizeof(T), LPR = 64 / EPV, RPI = 64 / LPR;
+    const char* mine = ml.template stage_out<T>(smem);
+    const int lane = lane_id(), chunk = lane % LPR, rsub = lane / LPR;
+    const int n = n0 + chunk * EPV;
+    for (int it = 0; it < 64 / RPI; ++it) {
+        const int row = it * RPI + rsub, m = m0 + row;
+        if (m < g.M && n < ncols)         // columns in [Nout, ncols) hold zeros (dT pitch padding)
+            *reinterpret_cast<Vec16<T>*>(o + (size_t)m * ldt + n) = *reinterpret_cast<const Vec16<T>*>(mine + row * P + chunk * 16);
+    }
+    if (ot) {
+        // the same tile transposed, dTt[class][sample] (pitch ldtt, multiple of the 16-byte vector): the embedding-gradient GEMM
+        // contracts over classes and wants class-major rows -- written here, a separate transpose pass (125 MB read + written at
+        // 122 000 classes) is not needed.  Lane = class row of the tile, eight 16-byte vectors of samples each.
+        const int cls = n0 + lane;
+        if (cls < g.Nout) {
 #pragma unroll
-                for (int v = 0; v < 64 / EPV; ++v) {
-                    Vec16<T> tv;
+            for (int v = 0; v < 64 / EPV; ++v) {
+                Vec16<T> tv;
 #pragma unroll
-                    for (int e = 0; e < EPV; ++e) tv.v[e] = *reinterpret_cast<const T*>(mine + (v * EPV + e) * P + lane * (int)sizeof(T));
-                    const int mcol = m0 + v * EPV;
-                    if (mcol < ldtt) *reinterpret_cast<Vec16<T>*>(ot + (size_t)cls * ldtt + mcol) = tv;      // rows past M hold zeros (masked above)
-                }
+                for (int e = 0; e < EPV; ++e) tv.v[e] = *reinterpret_cast<const T*>(mine + (v * EPV + e) * P + lane * (int)sizeof(T));
+                const int mcol = m0 + v * EPV;
+                if (mcol < ldtt) *reinterpret_cast<Vec16<T>*>(ot + (size_t)cls * ldtt + mcol) = tv;      // rows past M hold zeros (masked above)
             }
         }
     }
+}
+
+// One centre per class.  FWD: the forward partials; !FWD: the dT tile (compute dtype), and its transpose when dtt is set.
+template <typename T, bool FWD, int MK, bool FILT>
+__global__ __launch_bounds__(256, 2) void head_kernel(NtGeom g, const void* __restrict__ ehat,
+                                                             const void* __restrict__ what, const int* __restrict__ labels,
+                                                             MarginArg<MK, FILT> mc, float* __restrict__ part_max,
+                                                             float* __restrict__ part_sum, float* __restrict__ ztarget,
+                                                             const float* __restrict__ rowmax, const float* __restrict__ rowsum,
+                                                             float gscale, const float* __restrict__ upstream,
+                                                             void* __restrict__ dt, int ldt, void* __restrict__ dtt, int ldtt,
+                                                             int mtiles, int ntiles) {
+    typedef NtTile<T, 2, 2> Tile;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const uint32_t lin = xcd_remap(blockIdx.x, gridDim.x);
+    // mtile fastest: the (few) row tiles that share one weight tile run together on one XCD
+    const int mtile = (int)(lin % (uint32_t)mtiles), ntile = (int)(lin / (uint32_t)mtiles);
+    NtMainloop<T, 2, 2> ml;
+    ml.run(g, ehat, what, smem, mtile, ntile, 0, g.ksteps);
+
+    const int lane = lane_id(), wave = wave_id();
+    const int wm = wave >> 1, wn = wave & 1;
+    const int m0 = mtile * Tile::BM + wm * 64, n0 = ntile * Tile::BN + wn * 64;
+    // ntile * 2 + wn: the 64-class column group id
+    head_epilogue<FWD, MK, FILT, false>(lane, g, ml.acc, nullptr, m0, n0, ntile * 2 + wn, labels, mc, part_max, part_sum, ztarget, nullptr,
+                                        rowmax, rowsum, gscale, upstream);
+    if (!FWD) head_store_tile<T>(g, ml, smem, m0, n0, reinterpret_cast<T*>(dt), ldt, ldt, reinterpret_cast<T*>(dtt), ldtt);
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // Sub-centre variant (sub-center ArcFace, Deng et al., ECCV 2020): class c owns K centres, what[k * Nout + c] (plane-major: plane k is
 // a contiguous [Nout][D] table), and its cosine is the maximum over them.  The main loop runs once per plane against the same embedding
 // tile; a running element-wise maximum of the accumulators and the winning plane (2 bits per element, strict > when moving to a higher
-// plane: an exact tie stays with the lowest) are kept in registers, and the pooled tile enters the epilogue of head_kernel.  FWD and
+// plane: an exact tie stays with the lowest) are kept in registers, and the pooled tile enters head_epilogue.  FWD and
 // the recompute do the same arithmetic on the same operands in the same order, so they pick the same winner bit for bit.
 //   FWD : additionally tsub[m] = winning plane of row m's target, -1 for a row whose label is -1.
 //   !FWD: d = d loss / d cos_c from the pooled cosine, once; then K tiles, plane k holding d where it won and an exact 0 elsewhere:
 //         dT[m][k * ldp + c] (ldp = the planes' column pitch, a whole number of 16-byte vectors; columns [Nout, ldp) of a plane zero),
 //         dTt[k * Nout + c][m].
-// A kernel of its own, epilogue and all, rather than a switch inside head_kernel: with one centre per class the library launches exactly
-// the kernels it launched before, arguments and instruction streams unchanged.
+// A kernel of its own around the shared epilogue and tile store, not a switch inside head_kernel: the second accumulator tile and the
+// winner bits cost registers (189 - 253 VGPRs against 114 - 120, half the waves per SIMD), and with one centre per class the library
+// launches head_kernel with the arguments it always had.
 constexpr int HEAD_SUB_MAX = 4;              // winners are packed 2 bits each: 16 elements of one nt column per 32-bit register
 
 template <typename T, bool FWD, int MK, bool FILT>
@@ -303,90 +326,10 @@ __global__ __launch_bounds__(256, 2) void head_sub_kernel(NtGeom g, const void* 
 
     const int lane = lane_id(), wave = wave_id();
     const int wm = wave >> 1, wn = wave & 1;
-    const int fi = lane & 15, fg = lane >> 4;
     const int m0 = mtile * Tile::BM + wm * 64, n0 = ntile * Tile::BN + wn * 64;
-    const int group = ntile * 2 + wn;
-    if (!FWD && upstream) gscale *= upstream[0];
-
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-        const int m = m0 + mt * 16 + fi;
-        const bool mrow = m < g.M;
-        const int lab = mrow ? labels[m] : -1;
-        float gm = 0.f, gs = 1.f;
-        if (!FWD && mrow) { gm = rowmax[m]; gs = 1.f / rowsum[m]; }
-        [[maybe_unused]] float tlo, thi, m_ang = 0.f, m_add = 0.f;
-        if constexpr (MK == MG_ROWS) {
-            tlo = -1.f + mc.eps; thi = 1.f - mc.eps;
-            if (lab >= 0) { m_ang = mc.m_ang[m]; m_add = mc.m_add[m]; }
-        }
-        if (FWD && group == 0 && fg == 0 && mrow && lab < 0) tsub[m] = -1;
-        float z[4][4];
-        float vmax = -INFINITY;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int cls = n0 + nt * 16 + 4 * fg + e;
-                const float raw = best[nt][mt][e];
-                float t;
-                if constexpr (MK == MG_ROWS) t = fminf(fmaxf(raw, tlo), thi);
-                else t = fminf(fmaxf(raw, -1.f), 1.f);
-                float slope = 1.f;
-                bool filtered = false;
-                if (cls == lab) {
-                    if constexpr (MK == MG_ARC) {
-                        const float sin_t = sqrtf(1.f - t * t);
-                        if (t > mc.theta) { slope = mc.cos_m + t * mc.sin_m / sin_t; t = t * mc.cos_m - sin_t * mc.sin_m; }
-                        else t = t - mc.sinmm;
-                    } else if constexpr (MK == MG_ARC_EASY) {
-                        const float sin_t = sqrtf(1.f - t * t);
-                        if (t > 0.f) { slope = mc.cos_m + t * mc.sin_m / sin_t; t = t * mc.cos_m - sin_t * mc.sin_m; }
-                    } else if constexpr (MK == MG_ROWS) {
-                        t = rows_margin_target(t, m_ang, m_add, mc.eps, slope);
-                    } else {
-                        t = t - mc.m3;
-                    }
-                } else if constexpr (FILT) {
-                    if (t > mc.thr) { t = 0.f; filtered = true; }
-                }
-                const float zz = t * mc.s;
-                if (FWD) {
-                    z[nt][e] = (cls < g.Nout) ? zz : -INFINITY;          // the padded classes of the last tile never enter a sum
-                    vmax = fmaxf(vmax, z[nt][e]);
-                    if (cls == lab && mrow) { ztarget[m] = zz; tsub[m] = (int)((win[nt] >> (2 * (4 * mt + e))) & 3u); }
-                } else {
-                    float d = 0.f;
-                    if (cls < g.Nout && mrow) {
-                        const float p = __expf(zz - gm) * gs;
-                        bool inside;
-                        if constexpr (MK == MG_ROWS) inside = raw >= tlo && raw <= thi;
-                        else inside = raw >= -1.f && raw <= 1.f && !filtered;
-                        d = inside ? (p - (cls == lab ? 1.f : 0.f)) * gscale * mc.s * slope : 0.f;
-                    }
-                    best[nt][mt][e] = d;
-                }
-            }
-        if (FWD) {
-            vmax = lane_max_bit5(lane_max_bit4(vmax));
-            float vs = 0.f;
-            const float vref = vmax == -INFINITY ? 0.f : vmax;
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) vs += __expf(z[nt][e] - vref);
-            vs = lane_sum_bit5(lane_sum_bit4(vs));
-            if (fg == 0 && mrow) {
-                part_max[(size_t)group * g.M + m] = vmax;
-                part_sum[(size_t)group * g.M + m] = vs;
-            }
-        }
-    }
-    if (!FWD) {
-        constexpr int P = Tile::template stage_pitch<T>();
-        constexpr int EPV = 16 / (int)sizeof(T), LPR = 64 / EPV, RPI = 64 / LPR;
-        const int chunk = lane % LPR, rsub = lane / LPR;
-        const int n = n0 + chunk * EPV;
+    head_epilogue<FWD, MK, FILT, true>(lane, g, best, win, m0, n0, ntile * 2 + wn, labels, mc, part_max, part_sum, ztarget, tsub, rowmax,
+                                       rowsum, gscale, upstream);
+    if (!FWD)
         for (int k = 0; k < K; ++k) {
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt)
@@ -395,29 +338,10 @@ __global__ __launch_bounds__(256, 2) void head_sub_kernel(NtGeom g, const void* 
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
                         ml.acc[nt][mt][e] = ((win[nt] >> (2 * (4 * mt + e))) & 3u) == (uint32_t)k ? best[nt][mt][e] : 0.f;
-            const char* mine = ml.template stage_out<T>(smem);       // its leading barrier: the previous plane's tile has been read
-            T* o = reinterpret_cast<T*>(dt) + (size_t)k * ldp;
-            for (int it = 0; it < 64 / RPI; ++it) {
-                const int row = it * RPI + rsub, m = m0 + row;
-                if (m < g.M && n < ldp)         // columns [Nout, ldp) of the plane hold zeros
-                    *reinterpret_cast<Vec16<T>*>(o + (size_t)m * ldt + n) = *reinterpret_cast<const Vec16<T>*>(mine + row * P + chunk * 16);
-            }
-            if (dtt) {
-                T* ot = reinterpret_cast<T*>(dtt) + (size_t)k * g.Nout * ldtt;
-                const int cls = n0 + lane;
-                if (cls < g.Nout) {
-#pragma unroll
-                    for (int v = 0; v < 64 / EPV; ++v) {
-                        Vec16<T> tv;
-#pragma unroll
-                        for (int e = 0; e < EPV; ++e) tv.v[e] = *reinterpret_cast<const T*>(mine + (v * EPV + e) * P + lane * (int)sizeof(T));
-                        const int mcol = m0 + v * EPV;
-                        if (mcol < ldtt) *reinterpret_cast<Vec16<T>*>(ot + (size_t)cls * ldtt + mcol) = tv;
-                    }
-                }
-            }
+            // plane k: columns [Nout, ldp) of the plane hold zeros
+            head_store_tile<T>(g, ml, smem, m0, n0, reinterpret_cast<T*>(dt) + (size_t)k * ldp, ldt, ldp,
+                               dtt ? reinterpret_cast<T*>(dtt) + (size_t)k * g.Nout * ldtt : nullptr, ldtt);
         }
-    }
 }
 
 // rowmax[m] = max_g part_max[g][m]; rowsum[m] = sum_g part_sum[g][m] * exp(part_max[g][m] - rowmax[m])
@@ -505,95 +429,82 @@ __global__ void head_loss_kernel(const float* __restrict__ q, int N, float* __re
     if (threadIdx.x == 0) loss[0] = -red[0] / (float)N;
 }
 
+// the margin a launch runs with: the variant (mk, filt) and its kernel argument, ex for the descriptor variants, rows for MG_ROWS
+struct HeadMargin { int mk; bool filt; MarginConstEx ex; MarginRows rows; };
+
+template <int MK, bool FILT>
+static MarginArg<MK, FILT> margin_arg(const HeadMargin& hm) {
+    if constexpr (MK == MG_ROWS) return hm.rows;
+    else return hm.ex;                              // plain ArcFace: the MarginConst part only
+}
+
+// what the kernels take besides the geometry and the margin; a forward call leaves the backward's fields null and the other way round
+struct HeadArgs {
+    const void *ehat, *what;
+    const int* labels;
+    float *pmax, *psum, *zt;
+    int* tsub;
+    const float *rmax, *rsum;
+    float gscale;
+    const float* upstream;
+    void* dt;
+    int ldt, ldp;
+    void* dtt;
+    int ldtt;
+};
+
+// K = 0: head_kernel; K >= 1: head_sub_kernel over K planes
 template <typename T, bool FWD, int MK, bool FILT>
-static int head_launch_mk(const NtGeom& g, const void* ehat, const void* what, const int* labels, const MarginConstEx& mcx,
-                          float* pmax, float* psum, float* zt, const float* rmax, const float* rsum, float gscale,
-                          const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
+static int head_launch_mk(const NtGeom& g, const HeadArgs& a, const HeadMargin& hm, int K, hipStream_t stream) {
     typedef NtTile<T, 2, 2> Tile;
     const int mtiles = (g.M + Tile::BM - 1) / Tile::BM, ntiles = (g.Nout + Tile::BN - 1) / Tile::BN;
     const int lds = Tile::template lds_bytes<T>();
-    const MarginArg<MK, FILT> mc = mcx;           // plain ArcFace: the MarginConst part only
-    auto kern = head_kernel<T, FWD, MK, FILT>;
-    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "head")) return FRHIP_ELAUNCH;
-    hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(256), lds, stream, g, ehat, what, labels, mc, pmax, psum,
-                       zt, rmax, rsum, gscale, upstream, dt, ldt, dtt, ldtt, mtiles, ntiles);
-    return check_launch("head");
+    const MarginArg<MK, FILT> mc = margin_arg<MK, FILT>(hm);
+    auto plain = head_kernel<T, FWD, MK, FILT>;
+    auto sub = head_sub_kernel<T, FWD, MK, FILT>;
+    const char* who = K ? "head_sub" : "head";
+    if (set_dynamic_lds(K ? reinterpret_cast<const void*>(sub) : reinterpret_cast<const void*>(plain), lds, who)) return FRHIP_ELAUNCH;
+    if (K)
+        hipLaunchKernelGGL(sub, dim3(mtiles * ntiles), dim3(256), lds, stream, g, a.ehat, a.what, a.labels, mc, K, a.pmax, a.psum, a.zt,
+                           a.tsub, a.rmax, a.rsum, a.gscale, a.upstream, a.dt, a.ldt, a.ldp, a.dtt, a.ldtt, mtiles, ntiles);
+    else
+        hipLaunchKernelGGL(plain, dim3(mtiles * ntiles), dim3(256), lds, stream, g, a.ehat, a.what, a.labels, mc, a.pmax, a.psum, a.zt,
+                           a.rmax, a.rsum, a.gscale, a.upstream, a.dt, a.ldt, a.dtt, a.ldtt, mtiles, ntiles);
+    return check_launch(who);
 }
 
-// the per-row margin variant (its argument is not cut out of a MarginConstEx)
-template <typename T, bool FWD>
-static int head_launch_rows(const NtGeom& g, const void* ehat, const void* what, const int* labels, const MarginRows& mc,
-                            float* pmax, float* psum, float* zt, const float* rmax, const float* rsum, float gscale,
-                            const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
-    typedef NtTile<T, 2, 2> Tile;
-    const int mtiles = (g.M + Tile::BM - 1) / Tile::BM, ntiles = (g.Nout + Tile::BN - 1) / Tile::BN;
-    const int lds = Tile::template lds_bytes<T>();
-    auto kern = head_kernel<T, FWD, MG_ROWS, false>;
-    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "head")) return FRHIP_ELAUNCH;
-    hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(256), lds, stream, g, ehat, what, labels, mc, pmax, psum,
-                       zt, rmax, rsum, gscale, upstream, dt, ldt, dtt, ldtt, mtiles, ntiles);
-    return check_launch("head");
-}
-
-template <typename T, bool FWD>
-static int head_launch(const NtGeom& g, const void* ehat, const void* what, const int* labels, const MarginConstEx& mc, int mk, bool filt,
-                       float* pmax, float* psum, float* zt, const float* rmax, const float* rsum, float gscale,
-                       const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
+template <bool FWD>
+static int head_launch(int dtype, const NtGeom& g, const HeadArgs& a, const HeadMargin& hm, int K, hipStream_t stream) {
 #define HEAD_VARIANT(MKV, FV) \
-    if (mk == MKV && filt == FV) \
-        return head_launch_mk<T, FWD, MKV, FV>(g, ehat, what, labels, mc, pmax, psum, zt, rmax, rsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
+    if (hm.mk == MKV && hm.filt == FV) \
+        return dtype == FRHIP_DT_BF16 ? head_launch_mk<bf16_t, FWD, MKV, FV>(g, a, hm, K, stream) \
+                                      : head_launch_mk<float, FWD, MKV, FV>(g, a, hm, K, stream);
     HEAD_VARIANT(MG_ARC, false)
     HEAD_VARIANT(MG_ARC, true)
     HEAD_VARIANT(MG_ARC_EASY, false)
     HEAD_VARIANT(MG_ARC_EASY, true)
     HEAD_VARIANT(MG_COS, false)
     HEAD_VARIANT(MG_COS, true)
+    HEAD_VARIANT(MG_ROWS, false)
 #undef HEAD_VARIANT
-    set_error("head: unknown margin variant %d", mk);
+    set_error("head: unknown margin variant %d", hm.mk);
     return FRHIP_EINVAL;
 }
 
-// the sub-centre kernels: MC is MarginConstEx (descriptor margins; MarginArg cuts out what the variant takes) or MarginRows
-template <typename T, bool FWD, int MK, bool FILT, typename MC>
-static int head_sub_launch_mk(const NtGeom& g, const void* ehat, const void* what, const int* labels, const MC& mcx, int K,
-                              float* pmax, float* psum, float* zt, int* tsub, const float* rmax, const float* rsum, float gscale,
-                              const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt, hipStream_t stream) {
-    typedef NtTile<T, 2, 2> Tile;
-    const int mtiles = (g.M + Tile::BM - 1) / Tile::BM, ntiles = (g.Nout + Tile::BN - 1) / Tile::BN;
-    const int lds = Tile::template lds_bytes<T>();
-    const MarginArg<MK, FILT> mc = mcx;
-    auto kern = head_sub_kernel<T, FWD, MK, FILT>;
-    if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "head_sub")) return FRHIP_ELAUNCH;
-    hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(256), lds, stream, g, ehat, what, labels, mc, K, pmax, psum,
-                       zt, tsub, rmax, rsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, mtiles, ntiles);
-    return check_launch("head_sub");
-}
-
-template <typename T, bool FWD>
-static int head_sub_launch(const NtGeom& g, const void* ehat, const void* what, const int* labels, const MarginConstEx& mc, int mk,
-                           bool filt, int K, float* pmax, float* psum, float* zt, int* tsub, const float* rmax, const float* rsum,
-                           float gscale, const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt, hipStream_t stream) {
-#define HEAD_VARIANT(MKV, FV) \
-    if (mk == MKV && filt == FV) \
-        return head_sub_launch_mk<T, FWD, MKV, FV>(g, ehat, what, labels, mc, K, pmax, psum, zt, tsub, rmax, rsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
-    HEAD_VARIANT(MG_ARC, false)
-    HEAD_VARIANT(MG_ARC, true)
-    HEAD_VARIANT(MG_ARC_EASY, false)
-    HEAD_VARIANT(MG_ARC_EASY, true)
-    HEAD_VARIANT(MG_COS, false)
-    HEAD_VARIANT(MG_COS, true)
-#undef HEAD_VARIANT
-    set_error("head_sub: unknown margin variant %d", mk);
-    return FRHIP_EINVAL;
-}
-
-static int head_geom(NtGeom& g, int dtype, int n, int cl, int d, const char* who) {
+// sub: the entry points that take K centres per class (`cl` is the number of classes; what holds K * cl rows, plane-major)
+static int head_geom(NtGeom& g, int dtype, int n, int cl, int d, bool sub, int K, const char* who) {
+    if (sub && (K < 1 || K > HEAD_SUB_MAX)) {
+        set_error("%s: %d sub-centres per class (1 .. %d are supported)", who, K, HEAD_SUB_MAX);
+        return FRHIP_EINVAL;
+    }
     const int es = dtype == FRHIP_DT_BF16 ? 2 : 4, bke = NT_ROWB / es;
     if ((dtype != FRHIP_DT_BF16 && dtype != FRHIP_DT_F32) || n <= 0 || cl <= 0 || d <= 0 || (d % bke)) {
         set_error("%s: unsupported shape/dtype (n=%d classes=%d d=%d dtype=%d; d must be a multiple of %d)", who, n, cl, d, dtype, bke);
         return FRHIP_EINVAL;
     }
     if (1LL * cl * d * es > 0x7fffffffLL || 1LL * n * d * es > 0x7fffffffLL) { set_error("%s: operand exceeds 2 GiB", who); return FRHIP_EINVAL; }
+    // the GEMMs behind the recompute kernel read all K planes as one table
+    if (sub && 1LL * K * cl * d * es > 0x7fffffffLL) { set_error("%s: %d planes of %d classes exceed 2 GiB", who, K, cl); return FRHIP_EINVAL; }
     g.H = 1; g.W = 1; g.C = d; g.Ho = 1; g.Wo = 1; g.R = 1; g.S = 1; g.stride = 1; g.pad = 0; g.mode = 0;
     g.M = n; g.Nout = cl; g.Ktot = d; g.ksteps = d / bke; g.ksteps_per_split = g.ksteps;
     g.a_bytes = (uint32_t)(1LL * n * d * es); g.b_bytes = (uint32_t)(1LL * cl * d * es);
@@ -601,36 +512,75 @@ static int head_geom(NtGeom& g, int dtype, int n, int cl, int d, const char* who
     return FRHIP_OK;
 }
 
-static MarginConst margin_const(float s, float m) {
-    MarginConst mc;
-    const double pi = 3.14159265358979323846;
-    mc.s = s; mc.cos_m = (float)cos((double)m); mc.sin_m = (float)sin((double)m);
-    mc.theta = (float)cos(pi - (double)m); mc.sinmm = (float)(sin(pi - (double)m) * (double)m);
-    return mc;
+static int head_pitches(int dtype, int n, int cl, bool sub, int K, int ldt, int ldp, const void* dtt, int ldtt, const char* who) {
+    const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
+    if (sub && (ldp < cl || (ldp % epv) || 1LL * ldt < 1LL * K * ldp || (ldt % epv))) {
+        set_error("%s: bad dT pitches (row pitch %d, plane pitch %d, %d planes of %d classes)", who, ldt, ldp, K, cl);
+        return FRHIP_EINVAL;
+    }
+    if (!sub && (ldt < cl || (ldt % epv))) { set_error("%s: bad dT pitch %d", who, ldt); return FRHIP_EINVAL; }
+    if (dtt && (ldtt < n || (ldtt % epv))) { set_error("%s: bad transposed pitch %d", who, ldtt); return FRHIP_EINVAL; }
+    return FRHIP_OK;
 }
 
-// frhip_margin_t -> (constants, variant); FRHIP_EINVAL for a descriptor the kernels do not implement
-static int margin_desc(const frhip_margin_t* mg, MarginConstEx& mc, int& mk, bool& filt, const char* who) {
-    if (!mg || (mg->kind != FRHIP_MARGIN_ARCFACE && mg->kind != FRHIP_MARGIN_COSFACE) || !(mg->filter_thr >= 0.f)) {
+// descriptor -> (variant, constants); FRHIP_EINVAL for a descriptor the kernels do not implement
+static int margin_desc(const frhip_margin_t* mg, HeadMargin& hm, const char* who) {
+    if (!margin_desc_ok(mg)) {
         set_error("%s: bad margin descriptor (kind=%d thr=%g)", who, mg ? mg->kind : -1, mg ? (double)mg->filter_thr : 0.0);
         return FRHIP_EINVAL;
     }
     const bool arc = mg->kind == FRHIP_MARGIN_ARCFACE;
-    static_cast<MarginConst&>(mc) = margin_const(mg->s, arc ? mg->m : 0.f);
-    mc.m3 = arc ? 0.f : mg->m;
-    mc.thr = mg->filter_thr;
-    mk = arc ? (mg->easy ? MG_ARC_EASY : MG_ARC) : MG_COS;
-    filt = mg->filter_thr > 0.f;
+    static_cast<MarginConst&>(hm.ex) = margin_const(mg->s, arc ? mg->m : 0.f);
+    hm.ex.m3 = arc ? 0.f : mg->m;
+    hm.ex.thr = mg->filter_thr;
+    hm.mk = arc ? (mg->easy ? MG_ARC_EASY : MG_ARC) : MG_COS;
+    hm.filt = mg->filter_thr > 0.f;
     return FRHIP_OK;
 }
 
-static int margin_rows_desc(const frhip_margin_rows_t* mg, MarginRows& mc, const char* who) {
-    if (!mg || !mg->m_ang || !mg->m_add || !(mg->eps > 0.f && mg->eps < 0.5f)) {
+static int margin_desc(const frhip_margin_rows_t* mg, HeadMargin& hm, const char* who) {
+    if (!margin_rows_desc_ok(mg)) {
         set_error("%s: bad per-row margin descriptor (null pointer, or eps outside (0, 0.5))", who);
         return FRHIP_EINVAL;
     }
-    mc.s = mg->s; mc.eps = mg->eps; mc.m_ang = mg->m_ang; mc.m_add = mg->m_add;
+    hm.rows.s = mg->s; hm.rows.eps = mg->eps; hm.rows.m_ang = mg->m_ang; hm.rows.m_add = mg->m_add;
+    hm.mk = MG_ROWS;
+    hm.filt = false;
     return FRHIP_OK;
+}
+
+// The eight forward / recompute entry points.  D: frhip_margin_t or frhip_margin_rows_t.  sub = false: head_kernel (K is not read);
+// sub = true: head_sub_kernel over K planes, K = 1 included.  Every argument is validated before anything is launched.
+template <typename D>
+static int head_fwd_impl(const char* who, int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                         bool sub, int K, const D* margin, float* part_max, float* part_sum, float* ztarget, int* tsub, float* rowmax,
+                         float* rowsum, hipStream_t stream) {
+    NtGeom g;
+    HeadMargin hm = {};
+    int rc = head_geom(g, dtype, n, classes, d, sub, K, who);
+    if (rc || (rc = margin_desc(margin, hm, who))) return rc;
+    HeadArgs a = {};
+    a.ehat = ehat; a.what = what; a.labels = labels; a.pmax = part_max; a.psum = part_sum; a.zt = ztarget; a.tsub = tsub;
+    if ((rc = head_launch<true>(dtype, g, a, hm, sub ? K : 0, stream))) return rc;
+    hipLaunchKernelGGL(head_rowreduce_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, part_max, part_sum,
+                       frhip_head_groups(classes), n, rowmax, rowsum);
+    char tag[64];
+    snprintf(tag, sizeof(tag), "%s/rowreduce", who);
+    return check_launch(tag);
+}
+
+template <typename D>
+static int head_bwd_dt_impl(const char* who, int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                            bool sub, int K, const D* margin, const float* rowmax, const float* rowsum, float gscale,
+                            const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt, hipStream_t stream) {
+    NtGeom g;
+    HeadMargin hm = {};
+    int rc = head_geom(g, dtype, n, classes, d, sub, K, who);
+    if (rc || (rc = head_pitches(dtype, n, classes, sub, K, ldt, ldp, dtt, ldtt, who)) || (rc = margin_desc(margin, hm, who))) return rc;
+    HeadArgs a = {};
+    a.ehat = ehat; a.what = what; a.labels = labels; a.rmax = rowmax; a.rsum = rowsum; a.gscale = gscale; a.upstream = upstream;
+    a.dt = dt; a.ldt = ldt; a.ldp = ldp; a.dtt = dtt; a.ldtt = ldtt;
+    return head_launch<false>(dtype, g, a, hm, sub ? K : 0, stream);
 }
 
 // AdaFace's per-row margins from the embedding norms of the global batch (frhip_adaface_margins in frhip.h).  ONE block: n is a batch
@@ -688,126 +638,84 @@ extern "C" int frhip_adaface_margins(const float* norms, int n, double m, double
     return check_launch("frhip_adaface_margins");
 }
 
+extern "C" int frhip_head_sub_max(void) { return HEAD_SUB_MAX; }
+
+extern "C" int frhip_head_groups(int num_classes) { return ((num_classes + 127) / 128) * 2; }
+
+// ---- forward: one centre per class (head_kernel) ...
+extern "C" int frhip_head_fwd_ex(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                                 int d, const frhip_margin_t* margin, float* part_max, float* part_sum, float* ztarget,
+                                 float* rowmax, float* rowsum, hipStream_t stream) {
+    return head_fwd_impl("frhip_head_fwd", dtype, ehat, what, labels, n, classes, d, false, 1, margin, part_max, part_sum, ztarget, nullptr,
+                         rowmax, rowsum, stream);
+}
+
+extern "C" int frhip_head_fwd(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                              int d, float s, float m, float* part_max, float* part_sum, float* ztarget,
+                              float* rowmax, float* rowsum, hipStream_t stream) {
+    const frhip_margin_t mg = {FRHIP_MARGIN_ARCFACE, 0, s, m, 0.f};
+    return frhip_head_fwd_ex(dtype, ehat, what, labels, n, classes, d, &mg, part_max, part_sum, ztarget, rowmax, rowsum, stream);
+}
+
 extern "C" int frhip_head_fwd_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
                                    int d, const frhip_margin_rows_t* margin, float* part_max, float* part_sum, float* ztarget,
                                    float* rowmax, float* rowsum, hipStream_t stream) {
-    NtGeom g;
-    int rc = head_geom(g, dtype, n, classes, d, "frhip_head_fwd_rows");
-    if (rc) return rc;
-    MarginRows mc;
-    if ((rc = margin_rows_desc(margin, mc, "frhip_head_fwd_rows"))) return rc;
-    if (dtype == FRHIP_DT_BF16) rc = head_launch_rows<bf16_t, true>(g, ehat, what, labels, mc, part_max, part_sum, ztarget, nullptr, nullptr, 0.f, nullptr, nullptr, 0, nullptr, 0, stream);
-    else rc = head_launch_rows<float, true>(g, ehat, what, labels, mc, part_max, part_sum, ztarget, nullptr, nullptr, 0.f, nullptr, nullptr, 0, nullptr, 0, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(head_rowreduce_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, part_max, part_sum,
-                       frhip_head_groups(classes), n, rowmax, rowsum);
-    return check_launch("frhip_head_fwd_rows/rowreduce");
+    return head_fwd_impl("frhip_head_fwd_rows", dtype, ehat, what, labels, n, classes, d, false, 1, margin, part_max, part_sum, ztarget,
+                         nullptr, rowmax, rowsum, stream);
 }
 
-extern "C" int frhip_head_bwd_dt_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
-                                      int d, const frhip_margin_rows_t* margin, const float* rowmax, const float* rowsum, float gscale,
-                                      const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
-    NtGeom g;
-    int rc = head_geom(g, dtype, n, classes, d, "frhip_head_bwd_dt_rows");
-    if (rc) return rc;
-    const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
-    if (ldt < classes || (ldt % epv)) { set_error("frhip_head_bwd_dt_rows: bad dT pitch %d", ldt); return FRHIP_EINVAL; }
-    if (dtt && (ldtt < n || (ldtt % epv))) { set_error("frhip_head_bwd_dt_rows: bad transposed pitch %d", ldtt); return FRHIP_EINVAL; }
-    MarginRows mc;
-    if ((rc = margin_rows_desc(margin, mc, "frhip_head_bwd_dt_rows"))) return rc;
-    if (dtype == FRHIP_DT_BF16) return head_launch_rows<bf16_t, false>(g, ehat, what, labels, mc, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
-    return head_launch_rows<float, false>(g, ehat, what, labels, mc, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
-}
-
-// ---- K sub-centres per class.  `classes` is the number of classes; what holds K * classes rows, plane-major.
-static int head_sub_geom(NtGeom& g, int dtype, int n, int cl, int d, int K, const char* who) {
-    if (K < 1 || K > HEAD_SUB_MAX) { set_error("%s: %d sub-centres per class (1 .. %d are supported)", who, K, HEAD_SUB_MAX); return FRHIP_EINVAL; }
-    const int rc = head_geom(g, dtype, n, cl, d, who);
-    if (rc) return rc;
-    // the GEMMs behind the recompute kernel read all K planes as one table
-    if (1LL * K * cl * d * (dtype == FRHIP_DT_BF16 ? 2 : 4) > 0x7fffffffLL) {
-        set_error("%s: %d planes of %d classes exceed 2 GiB", who, K, cl);
-        return FRHIP_EINVAL;
-    }
-    return FRHIP_OK;
-}
-
-static int head_sub_pitches(int dtype, int n, int cl, int K, int ldt, int ldp, const void* dtt, int ldtt, const char* who) {
-    const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
-    if (ldp < cl || (ldp % epv) || 1LL * ldt < 1LL * K * ldp || (ldt % epv)) {
-        set_error("%s: bad dT pitches (row pitch %d, plane pitch %d, %d planes of %d classes)", who, ldt, ldp, K, cl);
-        return FRHIP_EINVAL;
-    }
-    if (dtt && (ldtt < n || (ldtt % epv))) { set_error("%s: bad transposed pitch %d", who, ldtt); return FRHIP_EINVAL; }
-    return FRHIP_OK;
-}
-
-extern "C" int frhip_head_sub_max(void) { return HEAD_SUB_MAX; }
-
+// ... and K sub-centres per class (head_sub_kernel).  `classes` is the number of classes; what holds K * classes rows, plane-major.
 extern "C" int frhip_head_fwd_sub(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
                                   int subcenters, const frhip_margin_t* margin, float* part_max, float* part_sum, float* ztarget,
                                   int* tsub, float* rowmax, float* rowsum, hipStream_t stream) {
-    NtGeom g;
-    int rc = head_sub_geom(g, dtype, n, classes, d, subcenters, "frhip_head_fwd_sub");
-    if (rc) return rc;
-    MarginConstEx mc;
-    int mk;
-    bool filt;
-    if ((rc = margin_desc(margin, mc, mk, filt, "frhip_head_fwd_sub"))) return rc;
-    if (dtype == FRHIP_DT_BF16) rc = head_sub_launch<bf16_t, true>(g, ehat, what, labels, mc, mk, filt, subcenters, part_max, part_sum, ztarget, tsub, nullptr, nullptr, 0.f, nullptr, nullptr, 0, 0, nullptr, 0, stream);
-    else rc = head_sub_launch<float, true>(g, ehat, what, labels, mc, mk, filt, subcenters, part_max, part_sum, ztarget, tsub, nullptr, nullptr, 0.f, nullptr, nullptr, 0, 0, nullptr, 0, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(head_rowreduce_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, part_max, part_sum,
-                       frhip_head_groups(classes), n, rowmax, rowsum);
-    return check_launch("frhip_head_fwd_sub/rowreduce");
+    return head_fwd_impl("frhip_head_fwd_sub", dtype, ehat, what, labels, n, classes, d, true, subcenters, margin, part_max, part_sum,
+                         ztarget, tsub, rowmax, rowsum, stream);
 }
 
 extern "C" int frhip_head_fwd_sub_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
                                        int subcenters, const frhip_margin_rows_t* margin, float* part_max, float* part_sum,
                                        float* ztarget, int* tsub, float* rowmax, float* rowsum, hipStream_t stream) {
-    NtGeom g;
-    int rc = head_sub_geom(g, dtype, n, classes, d, subcenters, "frhip_head_fwd_sub_rows");
-    if (rc) return rc;
-    MarginRows mc;
-    if ((rc = margin_rows_desc(margin, mc, "frhip_head_fwd_sub_rows"))) return rc;
-    if (dtype == FRHIP_DT_BF16) rc = head_sub_launch_mk<bf16_t, true, MG_ROWS, false>(g, ehat, what, labels, mc, subcenters, part_max, part_sum, ztarget, tsub, nullptr, nullptr, 0.f, nullptr, nullptr, 0, 0, nullptr, 0, stream);
-    else rc = head_sub_launch_mk<float, true, MG_ROWS, false>(g, ehat, what, labels, mc, subcenters, part_max, part_sum, ztarget, tsub, nullptr, nullptr, 0.f, nullptr, nullptr, 0, 0, nullptr, 0, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(head_rowreduce_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, part_max, part_sum,
-                       frhip_head_groups(classes), n, rowmax, rowsum);
-    return check_launch("frhip_head_fwd_sub_rows/rowreduce");
+    return head_fwd_impl("frhip_head_fwd_sub_rows", dtype, ehat, what, labels, n, classes, d, true, subcenters, margin, part_max,
+                         part_sum, ztarget, tsub, rowmax, rowsum, stream);
+}
+
+// ---- recompute (dT and its transpose), the same five
+extern "C" int frhip_head_bwd_dt_ex(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                                    int d, const frhip_margin_t* margin, const float* rowmax, const float* rowsum, float gscale,
+                                    const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
+    return head_bwd_dt_impl("frhip_head_bwd_dt", dtype, ehat, what, labels, n, classes, d, false, 1, margin, rowmax, rowsum, gscale,
+                            upstream, dt, ldt, 0, dtt, ldtt, stream);
+}
+
+extern "C" int frhip_head_bwd_dt(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                                 int d, float s, float m, const float* rowmax, const float* rowsum, float gscale,
+                                 const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
+    const frhip_margin_t mg = {FRHIP_MARGIN_ARCFACE, 0, s, m, 0.f};
+    return frhip_head_bwd_dt_ex(dtype, ehat, what, labels, n, classes, d, &mg, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
+}
+
+extern "C" int frhip_head_bwd_dt_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                                      int d, const frhip_margin_rows_t* margin, const float* rowmax, const float* rowsum, float gscale,
+                                      const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
+    return head_bwd_dt_impl("frhip_head_bwd_dt_rows", dtype, ehat, what, labels, n, classes, d, false, 1, margin, rowmax, rowsum, gscale,
+                            upstream, dt, ldt, 0, dtt, ldtt, stream);
 }
 
 extern "C" int frhip_head_bwd_dt_sub(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
                                      int subcenters, const frhip_margin_t* margin, const float* rowmax, const float* rowsum,
                                      float gscale, const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt,
                                      hipStream_t stream) {
-    NtGeom g;
-    int rc = head_sub_geom(g, dtype, n, classes, d, subcenters, "frhip_head_bwd_dt_sub");
-    if (rc) return rc;
-    if ((rc = head_sub_pitches(dtype, n, classes, subcenters, ldt, ldp, dtt, ldtt, "frhip_head_bwd_dt_sub"))) return rc;
-    MarginConstEx mc;
-    int mk;
-    bool filt;
-    if ((rc = margin_desc(margin, mc, mk, filt, "frhip_head_bwd_dt_sub"))) return rc;
-    if (dtype == FRHIP_DT_BF16) return head_sub_launch<bf16_t, false>(g, ehat, what, labels, mc, mk, filt, subcenters, nullptr, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
-    return head_sub_launch<float, false>(g, ehat, what, labels, mc, mk, filt, subcenters, nullptr, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
+    return head_bwd_dt_impl("frhip_head_bwd_dt_sub", dtype, ehat, what, labels, n, classes, d, true, subcenters, margin, rowmax, rowsum,
+                            gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
 }
 
 extern "C" int frhip_head_bwd_dt_sub_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
                                           int subcenters, const frhip_margin_rows_t* margin, const float* rowmax, const float* rowsum,
                                           float gscale, const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt,
                                           hipStream_t stream) {
-    NtGeom g;
-    int rc = head_sub_geom(g, dtype, n, classes, d, subcenters, "frhip_head_bwd_dt_sub_rows");
-    if (rc) return rc;
-    if ((rc = head_sub_pitches(dtype, n, classes, subcenters, ldt, ldp, dtt, ldtt, "frhip_head_bwd_dt_sub_rows"))) return rc;
-    MarginRows mc;
-    if ((rc = margin_rows_desc(margin, mc, "frhip_head_bwd_dt_sub_rows"))) return rc;
-    if (dtype == FRHIP_DT_BF16) return head_sub_launch_mk<bf16_t, false, MG_ROWS, false>(g, ehat, what, labels, mc, subcenters, nullptr, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
-    return head_sub_launch_mk<float, false, MG_ROWS, false>(g, ehat, what, labels, mc, subcenters, nullptr, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
+    return head_bwd_dt_impl("frhip_head_bwd_dt_sub_rows", dtype, ehat, what, labels, n, classes, d, true, subcenters, margin, rowmax,
+                            rowsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
 }
-
 extern "C" int frhip_l2norm_rows(int dtype, const float* x, void* xhat, float* norms, int rows, int d, float eps,
                                  hipStream_t stream) {
     if (d % 4) { set_error("frhip_l2norm_rows: d must be a multiple of 4"); return FRHIP_EINVAL; }
@@ -825,33 +733,6 @@ extern "C" int frhip_l2norm_bwd(int dtype, const float* dxhat, const void* xhat,
     else if (dtype == FRHIP_DT_F32) hipLaunchKernelGGL(l2norm_bwd_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, stream, dxhat, (const float*)xhat, norms, dx, rows, d, out_scale);
     else { set_error("frhip_l2norm_bwd: bad dtype %d", dtype); return FRHIP_EINVAL; }
     return check_launch("frhip_l2norm_bwd");
-}
-
-extern "C" int frhip_head_groups(int num_classes) { return ((num_classes + 127) / 128) * 2; }
-
-extern "C" int frhip_head_fwd_ex(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
-                                 int d, const frhip_margin_t* margin, float* part_max, float* part_sum, float* ztarget,
-                                 float* rowmax, float* rowsum, hipStream_t stream) {
-    NtGeom g;
-    int rc = head_geom(g, dtype, n, classes, d, "frhip_head_fwd");
-    if (rc) return rc;
-    MarginConstEx mc;
-    int mk;
-    bool filt;
-    if ((rc = margin_desc(margin, mc, mk, filt, "frhip_head_fwd"))) return rc;
-    if (dtype == FRHIP_DT_BF16) rc = head_launch<bf16_t, true>(g, ehat, what, labels, mc, mk, filt, part_max, part_sum, ztarget, nullptr, nullptr, 0.f, nullptr, nullptr, 0, nullptr, 0, stream);
-    else rc = head_launch<float, true>(g, ehat, what, labels, mc, mk, filt, part_max, part_sum, ztarget, nullptr, nullptr, 0.f, nullptr, nullptr, 0, nullptr, 0, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(head_rowreduce_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, part_max, part_sum,
-                       frhip_head_groups(classes), n, rowmax, rowsum);
-    return check_launch("frhip_head_fwd/rowreduce");
-}
-
-extern "C" int frhip_head_fwd(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
-                              int d, float s, float m, float* part_max, float* part_sum, float* ztarget,
-                              float* rowmax, float* rowsum, hipStream_t stream) {
-    const frhip_margin_t mg = {FRHIP_MARGIN_ARCFACE, 0, s, m, 0.f};
-    return frhip_head_fwd_ex(dtype, ehat, what, labels, n, classes, d, &mg, part_max, part_sum, ztarget, rowmax, rowsum, stream);
 }
 
 extern "C" int frhip_head_rescale(float* rowsum, const float* local_max, const float* global_max, int n, hipStream_t stream) {
@@ -881,28 +762,4 @@ extern "C" int frhip_head_merge_stats(const float* gathered, int world_size, int
 extern "C" int frhip_head_loss(const float* q, int n, float* loss, hipStream_t stream) {
     hipLaunchKernelGGL(head_loss_kernel, dim3(1), dim3(256), 0, stream, q, n, loss);
     return check_launch("frhip_head_loss");
-}
-
-extern "C" int frhip_head_bwd_dt(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
-                                 int d, float s, float m, const float* rowmax, const float* rowsum, float gscale,
-                                 const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
-    const frhip_margin_t mg = {FRHIP_MARGIN_ARCFACE, 0, s, m, 0.f};
-    return frhip_head_bwd_dt_ex(dtype, ehat, what, labels, n, classes, d, &mg, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
-}
-
-extern "C" int frhip_head_bwd_dt_ex(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
-                                    int d, const frhip_margin_t* margin, const float* rowmax, const float* rowsum, float gscale,
-                                    const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
-    NtGeom g;
-    int rc = head_geom(g, dtype, n, classes, d, "frhip_head_bwd_dt");
-    if (rc) return rc;
-    const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
-    if (ldt < classes || (ldt % epv)) { set_error("frhip_head_bwd_dt: bad dT pitch %d", ldt); return FRHIP_EINVAL; }
-    if (dtt && (ldtt < n || (ldtt % epv))) { set_error("frhip_head_bwd_dt: bad transposed pitch %d", ldtt); return FRHIP_EINVAL; }
-    MarginConstEx mc;
-    int mk;
-    bool filt;
-    if ((rc = margin_desc(margin, mc, mk, filt, "frhip_head_bwd_dt"))) return rc;
-    if (dtype == FRHIP_DT_BF16) return head_launch<bf16_t, false>(g, ehat, what, labels, mc, mk, filt, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
-    return head_launch<float, false>(g, ehat, what, labels, mc, mk, filt, nullptr, nullptr, nullptr, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
 }

@@ -5,7 +5,7 @@
 // HBM-bound row kernels: one 256-thread block per row, 16-byte accesses where the row pitch allows.
 #include "common.h"
 #include "cross_pair.h"
-#include "margin_rows.h"
+#include "margin_shared.h"
 #include "frhip.h"
 
 namespace frhip {
@@ -157,30 +157,27 @@ using namespace frhip;
 
 extern "C" int frhip_margin_fwd_ex(float* logits, const int64_t* labels, int n, int c, const frhip_margin_t* margin, float* tsave,
                                    uint64_t* filtered, hipStream_t stream) {
-    if (!margin || (margin->kind != FRHIP_MARGIN_ARCFACE && margin->kind != FRHIP_MARGIN_COSFACE) || !(margin->filter_thr >= 0.f) ||
-        (margin->filter_thr > 0.f && !filtered)) {
+    if (!margin_desc_ok(margin) || (margin->filter_thr > 0.f && !filtered)) {
         set_error("frhip_margin_fwd: bad margin descriptor or missing filter mask");
         return FRHIP_EINVAL;
     }
     if (n <= 0) return FRHIP_OK;
-    const double pi = 3.14159265358979323846, m = margin->m;
-    hipLaunchKernelGGL(margin_fwd_kernel, dim3(n), dim3(256), 0, stream, logits, labels, c, margin->s, (float)cos(m), (float)sin(m),
-                       (float)cos(pi - m), (float)(sin(pi - m) * m), margin->m, margin->kind, tsave, margin->easy,
-                       margin->filter_thr, margin->filter_thr > 0.f ? filtered : nullptr);
+    const MarginConst mc = margin_const(margin->s, margin->m);
+    hipLaunchKernelGGL(margin_fwd_kernel, dim3(n), dim3(256), 0, stream, logits, labels, c, mc.s, mc.cos_m, mc.sin_m, mc.theta, mc.sinmm,
+                       margin->m, margin->kind, tsave, margin->easy, margin->filter_thr, margin->filter_thr > 0.f ? filtered : nullptr);
     return check_launch("frhip_margin_fwd");
 }
 
 extern "C" int frhip_margin_bwd_ex(const float* gout, const int64_t* labels, const float* tsave, const uint64_t* filtered, int n, int c,
                                    const frhip_margin_t* margin, float* gin, hipStream_t stream) {
-    if (!margin || (margin->kind != FRHIP_MARGIN_ARCFACE && margin->kind != FRHIP_MARGIN_COSFACE) || !(margin->filter_thr >= 0.f) ||
-        (margin->filter_thr > 0.f && !filtered)) {
+    if (!margin_desc_ok(margin) || (margin->filter_thr > 0.f && !filtered)) {
         set_error("frhip_margin_bwd: bad margin descriptor or missing filter mask");
         return FRHIP_EINVAL;
     }
     if (n <= 0) return FRHIP_OK;
-    const double pi = 3.14159265358979323846, m = margin->m;
-    hipLaunchKernelGGL(margin_bwd_kernel, dim3(n), dim3(256), 0, stream, gout, labels, tsave, c, margin->s, (float)cos(m), (float)sin(m),
-                       (float)cos(pi - m), margin->kind, gin, margin->easy, margin->filter_thr > 0.f ? filtered : nullptr);
+    const MarginConst mc = margin_const(margin->s, margin->m);
+    hipLaunchKernelGGL(margin_bwd_kernel, dim3(n), dim3(256), 0, stream, gout, labels, tsave, c, mc.s, mc.cos_m, mc.sin_m, mc.theta,
+                       margin->kind, gin, margin->easy, margin->filter_thr > 0.f ? filtered : nullptr);
     return check_launch("frhip_margin_bwd");
 }
 
@@ -197,7 +194,7 @@ extern "C" int frhip_margin_bwd(const float* gout, const int64_t* labels, const 
 }
 
 static int margin_rows_args(const frhip_margin_rows_t* mg, const void* a, const void* b, const void* c, const void* d, const char* who) {
-    if (!mg || !mg->m_ang || !mg->m_add || !(mg->eps > 0.f && mg->eps < 0.5f) || !a || !b || !c || !d) {
+    if (!margin_rows_desc_ok(mg) || !a || !b || !c || !d) {
         set_error("%s: null pointer, or eps outside (0, 0.5)", who);
         return FRHIP_EINVAL;
     }

@@ -813,8 +813,21 @@ def _check_subcenters(what, subcenters):
     return k
 
 
-def _head_fwd_sub(ehat, what, labels_i32, s, m, margin, k):
-    """head_fwd with k > 1 centres per class (frhip_head_fwd_sub / _sub_rows) -> (ztarget, rowmax, rowsum, tsub)"""
+def _head_margin(margin, s, m, n, k):
+    """-> (entry-point suffix, descriptor or None) of a head call: margin=None with one centre per class takes the (s, m) entry point"""
+    if margin is None and k == 1:
+        return "", None
+    if margin is not None and _is_rows(margin):
+        return "_rows", _margin_rows_desc(margin, n)
+    return ("" if k > 1 else "_ex"), _margin_desc((MARGIN_ARCFACE, 0, s, m, 0.0) if margin is None else margin)
+
+
+def head_fwd(ehat, what, labels_i32, s, m, margin=None, subcenters=1):
+    """margin=None: ArcFace(s, m) (frhip_head_fwd); a (kind, easy, s, m, filter_thr) descriptor (frhip_head_fwd_ex); or per-row
+    margins (s, eps, m_ang, m_add), e.g. nets.ArcFace.RowMargins (frhip_head_fwd_rows).
+    subcenters = K > 1 (frhip_head_fwd_sub / _sub_rows): what holds K x classes rows, plane-major (row k * classes + c); a class's cosine is
+    the maximum over its K centres and the result gains tsub [n] int32, the winning centre of each row's target (-1: no target on this shard)."""
+    k = _check_subcenters(what, subcenters)
     n, d = ehat.shape
     classes = what.shape[0] // k
     groups = lib().frhip_head_groups(classes)
@@ -822,48 +835,18 @@ def _head_fwd_sub(ehat, what, labels_i32, s, m, margin, k):
     pm = torch.empty((groups, n), dtype=torch.float32, device=dev)
     ps = torch.empty((groups, n), dtype=torch.float32, device=dev)
     zt = torch.zeros((n,), dtype=torch.float32, device=dev)
-    tsub = torch.full((n,), -1, dtype=torch.int32, device=dev)
     rmax = torch.empty((n,), dtype=torch.float32, device=dev)
     rsum = torch.empty((n,), dtype=torch.float32, device=dev)
-    if margin is not None and _is_rows(margin):
-        desc = _margin_rows_desc(margin, n)
-        check(lib().frhip_head_fwd_sub_rows(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, k, ctypes.byref(desc), _p(pm),
-                                            _p(ps), _p(zt), _p(tsub), _p(rmax), _p(rsum), _s()), "frhip_head_fwd_sub_rows")
-    else:
-        desc = _margin_desc((MARGIN_ARCFACE, 0, s, m, 0.0) if margin is None else margin)
-        check(lib().frhip_head_fwd_sub(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, k, ctypes.byref(desc), _p(pm),
-                                       _p(ps), _p(zt), _p(tsub), _p(rmax), _p(rsum), _s()), "frhip_head_fwd_sub")
-    return zt, rmax, rsum, tsub
-
-
-def head_fwd(ehat, what, labels_i32, s, m, margin=None, subcenters=1):
-    """margin=None: ArcFace(s, m) (frhip_head_fwd); a (kind, easy, s, m, filter_thr) descriptor (frhip_head_fwd_ex); or per-row
-    margins (s, eps, m_ang, m_add), e.g. nets.ArcFace.RowMargins (frhip_head_fwd_rows).
-    subcenters = K > 1: what holds K x classes rows, plane-major (row k * classes + c); a class's cosine is the maximum over its K
-    centres and the result gains tsub [n] int32, the winning centre of each row's target (-1: no target on this shard)."""
-    k = _check_subcenters(what, subcenters)
+    suffix, desc = _head_margin(margin, s, m, n, k)
+    mg = (s, m) if desc is None else (ctypes.byref(desc),)
+    head = (dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d)
     if k > 1:
-        return _head_fwd_sub(ehat, what, labels_i32, s, m, margin, k)
-    n, d = ehat.shape
-    classes = what.shape[0]
-    groups = lib().frhip_head_groups(classes)
-    dev = ehat.device
-    pm = torch.empty((groups, n), dtype=torch.float32, device=dev)
-    ps = torch.empty((groups, n), dtype=torch.float32, device=dev)
-    zt = torch.zeros((n,), dtype=torch.float32, device=dev)
-    rmax = torch.empty((n,), dtype=torch.float32, device=dev)
-    rsum = torch.empty((n,), dtype=torch.float32, device=dev)
-    if margin is None:
-        check(lib().frhip_head_fwd(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, s, m, _p(pm), _p(ps),
-                                   _p(zt), _p(rmax), _p(rsum), _s()), "frhip_head_fwd")
-    elif _is_rows(margin):
-        desc = _margin_rows_desc(margin, n)
-        check(lib().frhip_head_fwd_rows(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, ctypes.byref(desc), _p(pm),
-                                        _p(ps), _p(zt), _p(rmax), _p(rsum), _s()), "frhip_head_fwd_rows")
-    else:
-        desc = _margin_desc(margin)
-        check(lib().frhip_head_fwd_ex(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, ctypes.byref(desc), _p(pm),
-                                      _p(ps), _p(zt), _p(rmax), _p(rsum), _s()), "frhip_head_fwd_ex")
+        tsub = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        name = "frhip_head_fwd_sub" + suffix
+        check(getattr(lib(), name)(*head, k, *mg, _p(pm), _p(ps), _p(zt), _p(tsub), _p(rmax), _p(rsum), _s()), name)
+        return zt, rmax, rsum, tsub
+    name = "frhip_head_fwd" + suffix
+    check(getattr(lib(), name)(*head, *mg, _p(pm), _p(ps), _p(zt), _p(rmax), _p(rsum), _s()), name)
     return zt, rmax, rsum
 
 
@@ -903,34 +886,6 @@ def head_loss(q):
 _DT_TAIL = 256
 
 
-def _head_bwd_dt_sub(ehat, what, labels_i32, s, m, rmax, rsum, gscale, upstream, transposed, margin, k):
-    n, d = ehat.shape
-    classes = what.shape[0] // k
-    e = epv(ehat.dtype)
-    ldp = (classes + e - 1) // e * e
-    # head_dw_sub hands the TN GEMMs one plane at a time, as a pointer k * ldp columns into dT with dT's row pitch.  Those kernels fetch whole
-    # column tiles (up to 256 columns, bounded by the pitch only) and drop what lies past their class count at the output; in the last row
-    # of a later plane the tail of such a tile lies behind dT.  _DT_TAIL zeroed elements behind it keep those reads inside the allocation.
-    flat = torch.empty((n * k * ldp + _DT_TAIL,), dtype=ehat.dtype, device=ehat.device)
-    flat[n * k * ldp:].zero_()
-    dt = flat[:n * k * ldp].view(n, k, ldp)
-    dtt, ldtt = None, 0
-    if transposed:
-        ldtt = (n + e - 1) // e * e
-        dtt = torch.empty((k * classes, ldtt), dtype=ehat.dtype, device=ehat.device)
-    if margin is not None and _is_rows(margin):
-        desc = _margin_rows_desc(margin, n)
-        check(lib().frhip_head_bwd_dt_sub_rows(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, k, ctypes.byref(desc),
-                                               _p(rmax), _p(rsum), gscale, _p(upstream), _p(dt), k * ldp, ldp, _p(dtt), ldtt, _s()),
-              "frhip_head_bwd_dt_sub_rows")
-    else:
-        desc = _margin_desc((MARGIN_ARCFACE, 0, s, m, 0.0) if margin is None else margin)
-        check(lib().frhip_head_bwd_dt_sub(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, k, ctypes.byref(desc),
-                                          _p(rmax), _p(rsum), gscale, _p(upstream), _p(dt), k * ldp, ldp, _p(dtt), ldtt, _s()),
-              "frhip_head_bwd_dt_sub")
-    return (dt, dtt) if transposed else dt
-
-
 def head_dw_sub(dt, ehat, what, wnorm, out_scale=1.0):
     """class-centre gradient [K x classes, d] fp32 from the K-plane dT [n, K, plane pitch] that head_bwd_dt(subcenters=K) returned (its
     allocation carries the tail the per-plane reads need: pass that tensor, not a copy): the kernels
@@ -968,28 +923,33 @@ def head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, gscale, upstream=None,
     subcenters = K > 1 (what: K x classes rows, plane-major): dT is [n][K][classes padded] -- plane k holds d loss / d cos where centre k
     won its (row, class) and an exact 0 elsewhere, pad columns 0 -- and dTt is [K x classes][n padded], row k * classes + c."""
     k = _check_subcenters(what, subcenters)
-    if k > 1:
-        return _head_bwd_dt_sub(ehat, what, labels_i32, s, m, rmax, rsum, gscale, upstream, transposed, margin, k)
     n, d = ehat.shape
-    classes = what.shape[0]
+    classes = what.shape[0] // k
     e = epv(ehat.dtype)
-    ldt = (classes + e - 1) // e * e
-    dt = torch.empty((n, ldt), dtype=ehat.dtype, device=ehat.device)
+    ldp = (classes + e - 1) // e * e
+    if k > 1:
+        # head_dw_sub hands the TN GEMMs one plane at a time, as a pointer k * ldp columns into dT with dT's row pitch.  Those kernels fetch whole
+        # column tiles (up to 256 columns, bounded by the pitch only) and drop what lies past their class count at the output; in the last row
+        # of a later plane the tail of such a tile lies behind dT.  _DT_TAIL zeroed elements behind it keep those reads inside the allocation.
+        flat = torch.empty((n * k * ldp + _DT_TAIL,), dtype=ehat.dtype, device=ehat.device)
+        flat[n * k * ldp:].zero_()
+        dt = flat[:n * k * ldp].view(n, k, ldp)
+    else:
+        dt = torch.empty((n, ldp), dtype=ehat.dtype, device=ehat.device)
     dtt, ldtt = None, 0
     if transposed:
         ldtt = (n + e - 1) // e * e
-        dtt = torch.empty((classes, ldtt), dtype=ehat.dtype, device=ehat.device)
-    if margin is None:
-        check(lib().frhip_head_bwd_dt(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, s, m, _p(rmax),
-                                      _p(rsum), gscale, _p(upstream), _p(dt), ldt, _p(dtt), ldtt, _s()), "frhip_head_bwd_dt")
-    elif _is_rows(margin):
-        desc = _margin_rows_desc(margin, n)
-        check(lib().frhip_head_bwd_dt_rows(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, ctypes.byref(desc), _p(rmax),
-                                           _p(rsum), gscale, _p(upstream), _p(dt), ldt, _p(dtt), ldtt, _s()), "frhip_head_bwd_dt_rows")
+        dtt = torch.empty((k * classes, ldtt), dtype=ehat.dtype, device=ehat.device)
+    suffix, desc = _head_margin(margin, s, m, n, k)
+    mg = (s, m) if desc is None else (ctypes.byref(desc),)
+    head = (dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d)
+    stats = (_p(rmax), _p(rsum), gscale, _p(upstream), _p(dt))
+    if k > 1:
+        name = "frhip_head_bwd_dt_sub" + suffix
+        check(getattr(lib(), name)(*head, k, *mg, *stats, k * ldp, ldp, _p(dtt), ldtt, _s()), name)
     else:
-        desc = _margin_desc(margin)
-        check(lib().frhip_head_bwd_dt_ex(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d, ctypes.byref(desc), _p(rmax),
-                                         _p(rsum), gscale, _p(upstream), _p(dt), ldt, _p(dtt), ldtt, _s()), "frhip_head_bwd_dt_ex")
+        name = "frhip_head_bwd_dt" + suffix
+        check(getattr(lib(), name)(*head, *mg, *stats, ldp, _p(dtt), ldtt, _s()), name)
     return (dt, dtt) if transposed else dt
 
 

@@ -59,9 +59,7 @@ class HipHeadKernels:
     def forward_stats(self, ehat, what, labels_i32, s, m, margin=None, subcenters=1):
         """margin: None = ArcFace(s, m); else a nets.ArcFace.Margin (CosFace, easy margin, interclass filtering) or RowMargins (AdaFace).
         subcenters = K > 1: what holds K x classes rows, plane-major, and the result gains tsub (the winning centre of every row's target)"""
-        if subcenters > 1:
-            return self.ops.head_fwd(ehat, what, labels_i32, s, m, margin=margin, subcenters=subcenters)
-        return self.ops.head_fwd(ehat, what, labels_i32, s, m, margin=margin)     # (ztarget, rowmax, rowsum) of this shard
+        return self.ops.head_fwd(ehat, what, labels_i32, s, m, margin=margin, subcenters=subcenters)   # (ztarget, rowmax, rowsum[, tsub]) of this shard
 
     def adaface_margins(self, norms, mg, batch_mean, batch_std, update):
         """-> (m_ang, m_add) [N] from the global batch's norms; update: batch_mean / batch_std are advanced in place first"""
@@ -88,29 +86,23 @@ class HipHeadKernels:
         weight-gradient GEMM: the caller starts the cross-rank reduce-scatter there and the two overlap."""
         ops = self.ops
         n, d = ehat.shape
-        classes = what.shape[0]
-        if subcenters > 1:
-            # the recompute kernel writes the gradient of a (row, class) into the winning centre's plane and exact zeros into the others: the
-            # GEMMs below then serve K x classes rows as they are (dE: one call over all planes; dW: plane by plane, ops.head_dw_sub)
-            dt, dtt = ops.head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, 1.0 / n_global, upstream, transposed=True, margin=margin,
-                                      subcenters=subcenters)
-            d_eh = torch.zeros((n, d), dtype=torch.float32, device=ehat.device)
-            ops.gemm_tn(dtt, what, d_eh, kc=n)
-            d_e = ops.l2norm_bwd(d_eh, ehat, enorm, out_scale=e_scale)
-            if on_de is not None:
-                on_de(d_e)
-            return d_e, ops.head_dw_sub(dt, ehat, what, wnorm)
-        # dT and its transpose from ONE launch (the embedding gradient contracts over classes, the weight gradient over samples)
-        dt, dtt = ops.head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, 1.0 / n_global, upstream, transposed=True, margin=margin)
+        # dT and its transpose from ONE launch (the embedding gradient contracts over classes, the weight gradient over samples).  With K > 1
+        # centres the recompute kernel writes the gradient of a (row, class) into the winning centre's plane and exact zeros into the others:
+        # the GEMMs below then serve K x classes rows as they are (dE: one call over all planes; dW: plane by plane, ops.head_dw_sub)
+        dt, dtt = ops.head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, 1.0 / n_global, upstream, transposed=True, margin=margin,
+                                  subcenters=subcenters)
         d_eh = torch.zeros((n, d), dtype=torch.float32, device=ehat.device)
         ops.gemm_tn(dtt, what, d_eh, kc=n)
         d_e = ops.l2norm_bwd(d_eh, ehat, enorm, out_scale=e_scale)
         if on_de is not None:
             on_de(d_e)
+        if subcenters > 1:
+            return d_e, ops.head_dw_sub(dt, ehat, what, wnorm)
         d_w = ops.head_dw(dt, ehat, what, wnorm)       # GEMM + normalise-backward in one launch (bf16, d = 512; 289 -> 191 us at 122 000 classes)
         if d_w is not None:
             return d_e, d_w
         # shapes head_dw does not serve: GEMM, then normalise-backward
+        classes = what.shape[0]
         d_wh = torch.empty((classes, d), dtype=torch.float32, device=ehat.device)
         ops.gemm_tn(dt, ehat, d_wh, kc=classes, overwrite=True)      # 250 MB at 122 000 classes: stored once, never zero-filled
         return d_e, ops.l2norm_bwd(d_wh, what, wnorm)

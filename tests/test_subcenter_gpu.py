@@ -149,6 +149,44 @@ def test_kernels_on_poisoned_memory(K, kind):
     _check_kernel_outputs(outs, labels, ref, K)
 
 
+@pytest.mark.parametrize("kind", ["arcface", "cosface_filt", "rows"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_one_centre_is_bit_identical_through_both_kernels(dtype, kind):
+    """head_kernel (ops.head_fwd / ops.head_bwd_dt) and head_sub_kernel with K = 1 (the _sub entry points called directly: ops sends one
+    centre per class to head_kernel) inline one epilogue and one tile store on the same accumulators, so every output agrees bit for bit;
+    tsub is 0 where the label is owned and -1 elsewhere.  Random unit rows, one label -1, one duplicate label."""
+    import ctypes
+    from frhip import ops
+    g = torch.Generator().manual_seed(4400)
+    emb, weight = torch.randn((N, D), generator=g), torch.randn((CLASSES, D), generator=g)
+    labels = torch.randint(0, CLASSES, (N,), generator=g)
+    labels[5], labels[9] = -1, labels[8]
+    mg = _margin(kind, N)[0]
+    eh, wh = ops.l2norm_rows(emb.cuda(), dtype)[0], ops.l2norm_rows(weight.cuda(), dtype)[0]
+    lab = labels.to(torch.int32).cuda()
+    zt, rmax, rsum = ops.head_fwd(eh, wh, lab, S, M, margin=mg)
+    dt, dtt = ops.head_bwd_dt(eh, wh, lab, S, M, rmax, rsum, 1.0 / N, transposed=True, margin=mg)
+
+    lib, p = ops.lib(), ops._p
+    if kind == "rows":
+        desc, fwd, bwd = ops._margin_rows_desc(mg, N), "frhip_head_fwd_sub_rows", "frhip_head_bwd_dt_sub_rows"
+    else:
+        desc = ops._margin_desc((ops.MARGIN_ARCFACE, 0, S, M, 0.0) if mg is None else mg)
+        fwd, bwd = "frhip_head_fwd_sub", "frhip_head_bwd_dt_sub"
+    part = torch.empty((2, lib.frhip_head_groups(CLASSES), N), dtype=torch.float32, device="cuda")
+    zt1, rmax1, rsum1 = torch.zeros(N, device="cuda"), torch.empty(N, device="cuda"), torch.empty(N, device="cuda")
+    tsub = torch.full((N,), -1, dtype=torch.int32, device="cuda")
+    dt1, dtt1 = torch.empty_like(dt), torch.empty_like(dtt)
+    head = (ops.dt_of(eh), p(eh), p(wh), p(lab), N, CLASSES, D, 1, ctypes.byref(desc))
+    ops.check(getattr(lib, fwd)(*head, p(part[0]), p(part[1]), p(zt1), p(tsub), p(rmax1), p(rsum1), ops._s()), fwd)
+    ldt = dt.shape[1]
+    ops.check(getattr(lib, bwd)(*head, p(rmax1), p(rsum1), 1.0 / N, None, p(dt1), ldt, ldt, p(dtt1), dtt.shape[1], ops._s()), bwd)
+    for name, a, b in (("ztarget", zt, zt1), ("rowmax", rmax, rmax1), ("rowsum", rsum, rsum1), ("dT", dt, dt1), ("dTt", dtt, dtt1)):
+        assert torch.equal(a, b), "%s: head_kernel and head_sub_kernel (K = 1) differ" % name
+    assert bool(dt.any()) and bool(torch.isfinite(rsum).all())
+    assert torch.equal(tsub.cpu(), torch.where(labels >= 0, 0, -1).to(torch.int32))
+
+
 # ------------------------------------------------------------------------------------------------ 2. the module, fp32 mode
 K3 = 3
 
