@@ -38,18 +38,22 @@ def _ctype(decl):
     raise ValueError("frhip.h: cannot map parameter %r" % decl)
 
 
-def parse_header(path=HEADER):
-    """-> {name: (restype, [argtypes])} for every function declared in frhip.h"""
+def prototypes(path=HEADER):
+    """-> [(return type, name, [parameter declarations])] for every function declared in frhip.h"""
     text = open(path).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
-    protos = {}
+    out = []
     for m in re.finditer(r"(const\s+char\s*\*|int)\s+(frhip_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
-        ret, name, args = m.group(1), m.group(2), m.group(3)
-        args = " ".join(args.split())
-        argtypes = [] if args in ("", "void") else [_ctype(a) for a in args.split(",")]
-        protos[name] = (ctypes.c_char_p if "char" in ret else ctypes.c_int, argtypes)
-    return protos
+        args = " ".join(m.group(3).split())
+        out.append((m.group(1), m.group(2), [] if args in ("", "void") else [a.strip() for a in args.split(",")]))
+    return out
+
+
+def parse_header(path=HEADER):
+    """-> {name: (restype, [argtypes])} for every function declared in frhip.h"""
+    return {name: (ctypes.c_char_p if "char" in ret else ctypes.c_int, [_ctype(a) for a in params])
+            for ret, name, params in prototypes(path)}
 
 
 _LIB = None

@@ -278,16 +278,15 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(T* __restrict__ mask,
 using namespace frhip;
 
 extern "C" int frhip_dropout_mask(int dtype, void* mask, size_t n, float keep, long long seed, hipStream_t stream) {
-    if (!(keep > 0.f) || keep > 1.f) { set_error("frhip_dropout_mask: keep probability %g outside (0, 1]", (double)keep); return FRHIP_EINVAL; }
-    if (n == 0) return FRHIP_OK;
-    size_t blocks = ((n + 3) / 4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL(dropout_mask_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, stream, (bf16_t*)mask, n, keep, 1.f / keep, (uint64_t)seed);
-    else if (dtype == FRHIP_DT_F32)
-        hipLaunchKernelGGL(dropout_mask_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, (float*)mask, n, keep, 1.f / keep, (uint64_t)seed);
-    else { set_error("frhip_dropout_mask: bad dtype %d", dtype); return FRHIP_EINVAL; }
-    return check_launch("frhip_dropout_mask");
+    return by_dtype(dtype, "frhip_dropout_mask", [&](auto t) {
+        typedef decltype(t) T;
+        if (!(keep > 0.f) || keep > 1.f) { set_error("frhip_dropout_mask: keep probability %g outside (0, 1]", (double)keep); return FRHIP_EINVAL; }
+        if (n == 0) return FRHIP_OK;
+        size_t blocks = ((n + 3) / 4 + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        hipLaunchKernelGGL(dropout_mask_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, stream, (T*)mask, n, keep, 1.f / keep, (uint64_t)seed);
+        return check_launch("frhip_dropout_mask");
+    });
 }
 
 static int augment_run(const uint8_t* in, float* out, const int32_t* flip, const int32_t* holes, const uint8_t* lut, int nholes,

@@ -584,30 +584,33 @@ extern "C" int frhip_colreduce_blocks(int rows, int c, int dtype) {
     return b;
 }
 
+// colreduce_kernel: column sums of x (forward statistics) or, with `bwd`, the two backward sums; row scale -> RS
+template <typename T>
+static int launch_colreduce(const char* who, int dtype, bool bwd, const void* x, const void* y, const float* mean, const float* invstd,
+                            const float* mask_scale, const float* mask_shift, const float* rowscale, int rows_per, int rows, int c,
+                            float* partial, hipStream_t stream) {
+    const auto k = rowscale ? colreduce_kernel<T, true, true> : bwd ? colreduce_kernel<T, true> : colreduce_kernel<T, false>;
+    hipLaunchKernelGGL(k, dim3(frhip_colreduce_blocks(rows, c, dtype)), dim3(EW_THREADS), 0, stream, (const T*)x, (const T*)y, mean,
+                       invstd, mask_scale, mask_shift, partial, rows, c, rowscale, rows_per);
+    return check_launch(who);
+}
+
 extern "C" int frhip_colstats(int dtype, const void* x, int rows, int c, float* partial, hipStream_t stream) {
-    if (!shape_ok(dtype, c, "frhip_colstats")) return FRHIP_EINVAL;
-    const int blocks = frhip_colreduce_blocks(rows, c, dtype);
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL((colreduce_kernel<bf16_t, false>), dim3(blocks), dim3(EW_THREADS), 0, stream,
-                           (const bf16_t*)x, nullptr, nullptr, nullptr, nullptr, nullptr, partial, rows, c);
-    else
-        hipLaunchKernelGGL((colreduce_kernel<float, false>), dim3(blocks), dim3(EW_THREADS), 0, stream,
-                           (const float*)x, nullptr, nullptr, nullptr, nullptr, nullptr, partial, rows, c);
-    return check_launch("frhip_colstats");
+    return by_dtype(dtype, "frhip_colstats", [&](auto t) {
+        if (!shape_ok(dtype, c, "frhip_colstats")) return FRHIP_EINVAL;
+        return launch_colreduce<decltype(t)>("frhip_colstats", dtype, false, x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1,
+                                         rows, c, partial, stream);
+    });
 }
 
 extern "C" int frhip_bn_bwd_reduce(int dtype, const void* dout, const void* y, const float* mean, const float* invstd,
                                    const float* mask_scale, const float* mask_shift, int rows, int c, float* partial,
                                    hipStream_t stream) {
-    if (!shape_ok(dtype, c, "frhip_bn_bwd_reduce")) return FRHIP_EINVAL;
-    const int blocks = frhip_colreduce_blocks(rows, c, dtype);
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL((colreduce_kernel<bf16_t, true>), dim3(blocks), dim3(EW_THREADS), 0, stream,
-                           (const bf16_t*)dout, (const bf16_t*)y, mean, invstd, mask_scale, mask_shift, partial, rows, c);
-    else
-        hipLaunchKernelGGL((colreduce_kernel<float, true>), dim3(blocks), dim3(EW_THREADS), 0, stream,
-                           (const float*)dout, (const float*)y, mean, invstd, mask_scale, mask_shift, partial, rows, c);
-    return check_launch("frhip_bn_bwd_reduce");
+    return by_dtype(dtype, "frhip_bn_bwd_reduce", [&](auto t) {
+        if (!shape_ok(dtype, c, "frhip_bn_bwd_reduce")) return FRHIP_EINVAL;
+        return launch_colreduce<decltype(t)>("frhip_bn_bwd_reduce", dtype, true, dout, y, mean, invstd, mask_scale, mask_shift, nullptr, 1,
+                                         rows, c, partial, stream);
+    });
 }
 
 // Up to FOLD_LIMIT partial rows go straight into the finalize kernel (16 lanes per channel, 4 rows in flight per lane);
@@ -623,23 +626,23 @@ static const float* fold_partials(const float* partial, int& nparts, int c, floa
     nparts = groups;
     return scratch;
 }
-static int fin_threads(int nparts) { return nparts > 64 ? 1024 : 256; }
-// folds of more than 64 rows by 256-thread blocks of 16 channels (rather than 1024-thread blocks of 64 channels)
-static bool fin_small(int nparts) { return nparts > 64; }
+// Folds the partial rows (scratch: 64*2*c floats), then one finalize launch: folds of more than 64 rows by 256-thread blocks of
+// 16 channels (`small`), the others by blocks of 64 channels.  `rest...` are the kernel's arguments behind (parts, nparts, c).
+template <typename K, typename... A>
+static int launch_finalize(const char* who, K small, K large, const float* partial, int nparts, float* scratch, int c, hipStream_t stream,
+                           A... rest) {
+    const float* p = fold_partials(partial, nparts, c, scratch, stream);
+    if (nparts > 64) hipLaunchKernelGGL(small, dim3((c + 15) / 16), dim3(256), 0, stream, p, nparts, c, rest...);
+    else hipLaunchKernelGGL(large, dim3((c + 63) / 64), dim3(256), 0, stream, p, nparts, c, rest...);
+    return check_launch(who);
+}
 
 extern "C" int frhip_bn_finalize(const float* partial, int nparts, float* scratch, int c, float count,
                                  const float* gamma, const float* beta, float* running_mean, float* running_var,
                                  float momentum, float eps, float* mean, float* invstd, float* scale, float* shift,
                                  hipStream_t stream) {
-    // scratch: 64*2*c floats
-    const float* p = fold_partials(partial, nparts, c, scratch, stream);
-    if (fin_small(nparts))
-        hipLaunchKernelGGL(bn_finalize_kernel<true>, dim3((c + 15) / 16), dim3(256), 0, stream, p, nparts, c, count, gamma, beta,
-                           running_mean, running_var, momentum, eps, mean, invstd, scale, shift);
-    else
-        hipLaunchKernelGGL(bn_finalize_kernel<false>, dim3((c + 63) / 64), dim3(fin_threads(nparts)), 0, stream, p, nparts, c, count, gamma, beta,
-                           running_mean, running_var, momentum, eps, mean, invstd, scale, shift);
-    return check_launch("frhip_bn_finalize");
+    return launch_finalize("frhip_bn_finalize", bn_finalize_kernel<true>, bn_finalize_kernel<false>, partial, nparts, scratch, c, stream,
+                           count, gamma, beta, running_mean, running_var, momentum, eps, mean, invstd, scale, shift);
 }
 
 extern "C" int frhip_bn_eval_affine(int c, const float* gamma, const float* beta, const float* running_mean,
@@ -682,160 +685,108 @@ extern "C" int frhip_bn_eval_state(int c, const float* gamma, const float* beta,
 extern "C" int frhip_bn_bwd_finalize_eval(const float* partial, int nparts, float* scratch, int c, float count,
                                           const float* gamma, const float* mean, const float* invstd, float* dgamma,
                                           float* dbeta, float* ca, float* cb, float* cc, hipStream_t stream) {
-    const float* p = fold_partials(partial, nparts, c, scratch, stream);
-    if (fin_small(nparts))
-        hipLaunchKernelGGL((bn_bwd_finalize_kernel<true, true>), dim3((c + 15) / 16), dim3(256), 0, stream, p, nparts, c, count, gamma,
-                           mean, invstd, dgamma, dbeta, ca, cb, cc);
-    else
-        hipLaunchKernelGGL((bn_bwd_finalize_kernel<false, true>), dim3((c + 63) / 64), dim3(fin_threads(nparts)), 0, stream, p, nparts, c,
-                           count, gamma, mean, invstd, dgamma, dbeta, ca, cb, cc);
-    return check_launch("frhip_bn_bwd_finalize_eval");
+    return launch_finalize("frhip_bn_bwd_finalize_eval", bn_bwd_finalize_kernel<true, true>, bn_bwd_finalize_kernel<false, true>, partial,
+                           nparts, scratch, c, stream, count, gamma, mean, invstd, dgamma, dbeta, ca, cb, cc);
 }
 
 extern "C" int frhip_bn_bwd_finalize(const float* partial, int nparts, float* scratch, int c, float count,
                                      const float* gamma, const float* mean, const float* invstd, float* dgamma,
                                      float* dbeta, float* ca, float* cb, float* cc, hipStream_t stream) {
-    const float* p = fold_partials(partial, nparts, c, scratch, stream);
-    if (fin_small(nparts))
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel<true>, dim3((c + 15) / 16), dim3(256), 0, stream, p, nparts, c, count, gamma,
-                           mean, invstd, dgamma, dbeta, ca, cb, cc);
-    else
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel<false>, dim3((c + 63) / 64), dim3(fin_threads(nparts)), 0, stream, p, nparts, c, count, gamma,
-                           mean, invstd, dgamma, dbeta, ca, cb, cc);
-    return check_launch("frhip_bn_bwd_finalize");
+    return launch_finalize("frhip_bn_bwd_finalize", bn_bwd_finalize_kernel<true>, bn_bwd_finalize_kernel<false>, partial, nparts, scratch,
+                           c, stream, count, gamma, mean, invstd, dgamma, dbeta, ca, cb, cc);
+}
+
+// The row-streaming element-wise launch: the batched kernel `kb` (which takes rows_per_block in front of the row scale) when
+// g_ew_batch, otherwise the row-at-a-time kernel `kr`.  `a...` are the arguments the two share, up to (rows, c).
+template <typename KB, typename KR, typename... A>
+static int launch_ew(const char* who, int dtype, KB kb, KR kr, int rows, int c, const float* rowscale, int rows_per, hipStream_t stream,
+                     A... a) {
+    if (g_ew_batch) {
+        int rpb;
+        const int blocks = ew_batched_blocks(rows, c, dtype, rpb);
+        hipLaunchKernelGGL(kb, dim3(blocks), dim3(EW_THREADS), 0, stream, a..., rows, c, rpb, rowscale, rows_per);
+    } else {
+        hipLaunchKernelGGL(kr, dim3(ew_row_blocks(rows, c, dtype)), dim3(EW_THREADS), 0, stream, a..., rows, c, rowscale, rows_per);
+    }
+    return check_launch(who);
+}
+
+// bn_apply_kernel / bn_apply_batched_kernel.  Choice of loads: row scale -> RS with plain loads; in place -> the instantiation that
+// reads through `out` (plain loads and stores); residual -> non-temporal loads; else plain.
+template <typename T>
+static int launch_bn_apply(const char* who, int dtype, const void* y, const float* scale, const float* shift, const void* res,
+                           const float* res_scale, const float* res_shift, int relu, const float* rowscale, int rows_per, void* out,
+                           int rows, int c, hipStream_t stream) {
+    const bool inplace = !rowscale && y == out;
+    const auto kb = rowscale ? bn_apply_batched_kernel<T, false, true> : inplace ? bn_apply_batched_kernel<T, false, false, true>
+                    : res ? bn_apply_batched_kernel<T, true> : bn_apply_batched_kernel<T, false>;
+    const auto kr = rowscale ? bn_apply_kernel<T, false, true> : inplace ? bn_apply_kernel<T, false, false, true>
+                    : res ? bn_apply_kernel<T, true> : bn_apply_kernel<T, false>;
+    return launch_ew(who, dtype, kb, kr, rows, c, rowscale, rows_per, stream, inplace ? nullptr : (const T*)y, scale, shift,
+                     (const T*)res, res_scale, res_shift, relu, (T*)out);
+}
+
+// bn_bwd_apply_kernel / bn_bwd_apply_batched_kernel: non-temporal loads, except under a row scale (RS, plain loads)
+template <typename T>
+static int launch_bn_bwd_apply(const char* who, int dtype, const void* dout, const void* y, const float* ca, const float* cb,
+                               const float* cc, const float* mask_scale, const float* mask_shift, const float* rowscale, int rows_per,
+                               void* dy, int rows, int c, hipStream_t stream) {
+    const auto kb = rowscale ? bn_bwd_apply_batched_kernel<T, false, true> : bn_bwd_apply_batched_kernel<T, true>;
+    const auto kr = rowscale ? bn_bwd_apply_kernel<T, false, true> : bn_bwd_apply_kernel<T, true>;
+    return launch_ew(who, dtype, kb, kr, rows, c, rowscale, rows_per, stream, (const T*)dout, (const T*)y, ca, cb, cc, mask_scale,
+                     mask_shift, (T*)dy);
 }
 
 // Stochastic-depth variants (nets/AlterNet_SwinV2_FAN.py: x + drop_path(norm(branch))): rowscale[g] multiplies the normalised branch
 // (forward) / the incoming gradient (backward) of the rows_per consecutive rows of sample g.  Plain-load instantiations only.
 extern "C" int frhip_bn_apply_rs(int dtype, const void* y, const float* scale, const float* shift, const void* res,
                                  const float* rowscale, int rows_per, void* out, int rows, int c, hipStream_t stream) {
-    if (!shape_ok(dtype, c, "frhip_bn_apply_rs")) return FRHIP_EINVAL;
-    if (!rowscale || rows_per <= 0) { set_error("frhip_bn_apply_rs: rowscale and rows_per are required"); return FRHIP_EINVAL; }
-    if (g_ew_batch) {
-        int rpb;
-        const int blocks = ew_batched_blocks(rows, c, dtype, rpb);
-        if (dtype == FRHIP_DT_BF16)
-            hipLaunchKernelGGL((bn_apply_batched_kernel<bf16_t, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)y, scale,
-                               shift, (const bf16_t*)res, nullptr, nullptr, 0, (bf16_t*)out, rows, c, rpb, rowscale, rows_per);
-        else
-            hipLaunchKernelGGL((bn_apply_batched_kernel<float, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const float*)y, scale,
-                               shift, (const float*)res, nullptr, nullptr, 0, (float*)out, rows, c, rpb, rowscale, rows_per);
-        return check_launch("frhip_bn_apply_rs");
-    }
-    const int blocks = ew_row_blocks(rows, c, dtype);
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL((bn_apply_kernel<bf16_t, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)y, scale,
-                           shift, (const bf16_t*)res, nullptr, nullptr, 0, (bf16_t*)out, rows, c, rowscale, rows_per);
-    else
-        hipLaunchKernelGGL((bn_apply_kernel<float, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const float*)y, scale,
-                           shift, (const float*)res, nullptr, nullptr, 0, (float*)out, rows, c, rowscale, rows_per);
-    return check_launch("frhip_bn_apply_rs");
+    return by_dtype(dtype, "frhip_bn_apply_rs", [&](auto t) {
+        if (!shape_ok(dtype, c, "frhip_bn_apply_rs")) return FRHIP_EINVAL;
+        if (!rowscale || rows_per <= 0) { set_error("frhip_bn_apply_rs: rowscale and rows_per are required"); return FRHIP_EINVAL; }
+        return launch_bn_apply<decltype(t)>("frhip_bn_apply_rs", dtype, y, scale, shift, res, nullptr, nullptr, 0, rowscale, rows_per, out,
+                                        rows, c, stream);
+    });
 }
 
 extern "C" int frhip_bn_bwd_reduce_rs(int dtype, const void* dout, const void* y, const float* mean, const float* invstd,
                                       const float* rowscale, int rows_per, int rows, int c, float* partial, hipStream_t stream) {
-    if (!shape_ok(dtype, c, "frhip_bn_bwd_reduce_rs")) return FRHIP_EINVAL;
-    if (!rowscale || rows_per <= 0) { set_error("frhip_bn_bwd_reduce_rs: rowscale and rows_per are required"); return FRHIP_EINVAL; }
-    const int blocks = frhip_colreduce_blocks(rows, c, dtype);
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL((colreduce_kernel<bf16_t, true, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)dout,
-                           (const bf16_t*)y, mean, invstd, nullptr, nullptr, partial, rows, c, rowscale, rows_per);
-    else
-        hipLaunchKernelGGL((colreduce_kernel<float, true, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const float*)dout,
-                           (const float*)y, mean, invstd, nullptr, nullptr, partial, rows, c, rowscale, rows_per);
-    return check_launch("frhip_bn_bwd_reduce_rs");
+    return by_dtype(dtype, "frhip_bn_bwd_reduce_rs", [&](auto t) {
+        if (!shape_ok(dtype, c, "frhip_bn_bwd_reduce_rs")) return FRHIP_EINVAL;
+        if (!rowscale || rows_per <= 0) { set_error("frhip_bn_bwd_reduce_rs: rowscale and rows_per are required"); return FRHIP_EINVAL; }
+        return launch_colreduce<decltype(t)>("frhip_bn_bwd_reduce_rs", dtype, true, dout, y, mean, invstd, nullptr, nullptr, rowscale,
+                                         rows_per, rows, c, partial, stream);
+    });
 }
 
 extern "C" int frhip_bn_bwd_apply_rs(int dtype, const void* dout, const void* y, const float* ca, const float* cb, const float* cc,
                                      const float* rowscale, int rows_per, void* dy, int rows, int c, hipStream_t stream) {
-    if (!shape_ok(dtype, c, "frhip_bn_bwd_apply_rs")) return FRHIP_EINVAL;
-    if (!rowscale || rows_per <= 0) { set_error("frhip_bn_bwd_apply_rs: rowscale and rows_per are required"); return FRHIP_EINVAL; }
-    if (g_ew_batch) {
-        int rpb;
-        const int blocks = ew_batched_blocks(rows, c, dtype, rpb);
-        if (dtype == FRHIP_DT_BF16)
-            hipLaunchKernelGGL((bn_bwd_apply_batched_kernel<bf16_t, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)dout,
-                               (const bf16_t*)y, ca, cb, cc, nullptr, nullptr, (bf16_t*)dy, rows, c, rpb, rowscale, rows_per);
-        else
-            hipLaunchKernelGGL((bn_bwd_apply_batched_kernel<float, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const float*)dout,
-                               (const float*)y, ca, cb, cc, nullptr, nullptr, (float*)dy, rows, c, rpb, rowscale, rows_per);
-        return check_launch("frhip_bn_bwd_apply_rs");
-    }
-    const int blocks = ew_row_blocks(rows, c, dtype);
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)dout,
-                           (const bf16_t*)y, ca, cb, cc, nullptr, nullptr, (bf16_t*)dy, rows, c, rowscale, rows_per);
-    else
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const float*)dout,
-                           (const float*)y, ca, cb, cc, nullptr, nullptr, (float*)dy, rows, c, rowscale, rows_per);
-    return check_launch("frhip_bn_bwd_apply_rs");
+    return by_dtype(dtype, "frhip_bn_bwd_apply_rs", [&](auto t) {
+        if (!shape_ok(dtype, c, "frhip_bn_bwd_apply_rs")) return FRHIP_EINVAL;
+        if (!rowscale || rows_per <= 0) { set_error("frhip_bn_bwd_apply_rs: rowscale and rows_per are required"); return FRHIP_EINVAL; }
+        return launch_bn_bwd_apply<decltype(t)>("frhip_bn_bwd_apply_rs", dtype, dout, y, ca, cb, cc, nullptr, nullptr, rowscale, rows_per,
+                                            dy, rows, c, stream);
+    });
 }
 
 extern "C" int frhip_bn_apply(int dtype, const void* y, const float* scale, const float* shift, const void* res,
                               const float* res_scale, const float* res_shift, int relu, void* out, int rows, int c,
                               hipStream_t stream) {
-    if (!shape_ok(dtype, c, "frhip_bn_apply")) return FRHIP_EINVAL;
-    if (g_ew_batch) {          // same choice of loads as below: in place -> plain, through `out`; residual -> non-temporal; else plain
-        int rpb;
-        const int nblocks = ew_batched_blocks(rows, c, dtype, rpb);
-#define BN_APPLY_BATCHED(T)                                                                                                   \
-        do { if (y == out)                                                                                                    \
-            hipLaunchKernelGGL((bn_apply_batched_kernel<T, false, false, true>), dim3(nblocks), dim3(EW_THREADS), 0, stream, nullptr, \
-                               scale, shift, (const T*)res, res_scale, res_shift, relu, (T*)out, rows, c, rpb);                \
-        else if (res)                                                                                                         \
-            hipLaunchKernelGGL((bn_apply_batched_kernel<T, true>), dim3(nblocks), dim3(EW_THREADS), 0, stream, (const T*)y,   \
-                               scale, shift, (const T*)res, res_scale, res_shift, relu, (T*)out, rows, c, rpb);                \
-        else                                                                                                                  \
-            hipLaunchKernelGGL((bn_apply_batched_kernel<T, false>), dim3(nblocks), dim3(EW_THREADS), 0, stream, (const T*)y,  \
-                               scale, shift, (const T*)res, res_scale, res_shift, relu, (T*)out, rows, c, rpb); } while (0)
-        if (dtype == FRHIP_DT_BF16) BN_APPLY_BATCHED(bf16_t); else BN_APPLY_BATCHED(float);
-#undef BN_APPLY_BATCHED
-        return check_launch("frhip_bn_apply");
-    }
-    const int blocks = ew_row_blocks(rows, c, dtype);
-#define BN_APPLY_GO(T, L)                                                                                                     \
-    hipLaunchKernelGGL((bn_apply_kernel<T, L>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const T*)y, scale, shift,        \
-                       (const T*)res, res_scale, res_shift, relu, (T*)out, rows, c)
-#define BN_APPLY_PICK(T)                                                                                                      \
-    do { if (res) BN_APPLY_GO(T, true); else BN_APPLY_GO(T, false); } while (0)      // non-temporal loads in the residual pass
-    if (y == out) {            // in place: the instantiation that reads through `out` (plain loads and stores)
-        if (dtype == FRHIP_DT_BF16)
-            hipLaunchKernelGGL((bn_apply_kernel<bf16_t, false, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, nullptr, scale, shift,
-                               (const bf16_t*)res, res_scale, res_shift, relu, (bf16_t*)out, rows, c);
-        else
-            hipLaunchKernelGGL((bn_apply_kernel<float, false, false, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, nullptr, scale, shift,
-                               (const float*)res, res_scale, res_shift, relu, (float*)out, rows, c);
-        return check_launch("frhip_bn_apply");
-    }
-    if (dtype == FRHIP_DT_BF16) BN_APPLY_PICK(bf16_t); else BN_APPLY_PICK(float);
-#undef BN_APPLY_PICK
-#undef BN_APPLY_GO
-    return check_launch("frhip_bn_apply");
+    return by_dtype(dtype, "frhip_bn_apply", [&](auto t) {
+        if (!shape_ok(dtype, c, "frhip_bn_apply")) return FRHIP_EINVAL;
+        return launch_bn_apply<decltype(t)>("frhip_bn_apply", dtype, y, scale, shift, res, res_scale, res_shift, relu, nullptr, 1, out,
+                                        rows, c, stream);
+    });
 }
 
 extern "C" int frhip_bn_bwd_apply(int dtype, const void* dout, const void* y, const float* ca, const float* cb,
                                   const float* cc, const float* mask_scale, const float* mask_shift, void* dy,
                                   int rows, int c, hipStream_t stream) {
-    if (!shape_ok(dtype, c, "frhip_bn_bwd_apply")) return FRHIP_EINVAL;
-    if (g_ew_batch) {
-        int rpb;
-        const int nblocks = ew_batched_blocks(rows, c, dtype, rpb);
-        if (dtype == FRHIP_DT_BF16)
-            hipLaunchKernelGGL((bn_bwd_apply_batched_kernel<bf16_t, true>), dim3(nblocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)dout,
-                               (const bf16_t*)y, ca, cb, cc, mask_scale, mask_shift, (bf16_t*)dy, rows, c, rpb);
-        else
-            hipLaunchKernelGGL((bn_bwd_apply_batched_kernel<float, true>), dim3(nblocks), dim3(EW_THREADS), 0, stream, (const float*)dout,
-                               (const float*)y, ca, cb, cc, mask_scale, mask_shift, (float*)dy, rows, c, rpb);
-        return check_launch("frhip_bn_bwd_apply");
-    }
-    const int blocks = ew_row_blocks(rows, c, dtype);
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const bf16_t*)dout,
-                           (const bf16_t*)y, ca, cb, cc, mask_scale, mask_shift, (bf16_t*)dy, rows, c);
-    else
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true>), dim3(blocks), dim3(EW_THREADS), 0, stream, (const float*)dout,
-                           (const float*)y, ca, cb, cc, mask_scale, mask_shift, (float*)dy, rows, c);
-    return check_launch("frhip_bn_bwd_apply");
+    return by_dtype(dtype, "frhip_bn_bwd_apply", [&](auto t) {
+        if (!shape_ok(dtype, c, "frhip_bn_bwd_apply")) return FRHIP_EINVAL;
+        return launch_bn_bwd_apply<decltype(t)>("frhip_bn_bwd_apply", dtype, dout, y, ca, cb, cc, mask_scale, mask_shift, nullptr, 1, dy,
+                                            rows, c, stream);
+    });
 }
 
 extern "C" int frhip_sum_partials(const float* partial, int nparts, int c, int which, float* out_accum, hipStream_t stream) {
@@ -850,17 +801,17 @@ extern "C" int frhip_add_bias(float* x, const float* bias, int rows, int c, hipS
 }
 
 extern "C" int frhip_cast_from_f32(int dtype, const float* src, void* dst, size_t n, hipStream_t stream) {
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL(cast_from_f32_kernel<bf16_t>, dim3(grid_for(n, 256)), dim3(256), 0, stream, src, (bf16_t*)dst, n);
-    else
-        hipLaunchKernelGGL(cast_from_f32_kernel<float>, dim3(grid_for(n, 256)), dim3(256), 0, stream, src, (float*)dst, n);
-    return check_launch("frhip_cast_from_f32");
+    return by_dtype(dtype, "frhip_cast_from_f32", [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(cast_from_f32_kernel<T>, dim3(grid_for(n, 256)), dim3(256), 0, stream, src, (T*)dst, n);
+        return check_launch("frhip_cast_from_f32");
+    });
 }
 
 extern "C" int frhip_cast_to_f32(int dtype, const void* src, float* dst, size_t n, hipStream_t stream) {
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL(cast_to_f32_kernel<bf16_t>, dim3(grid_for(n, 256)), dim3(256), 0, stream, (const bf16_t*)src, dst, n);
-    else
-        hipLaunchKernelGGL(cast_to_f32_kernel<float>, dim3(grid_for(n, 256)), dim3(256), 0, stream, (const float*)src, dst, n);
-    return check_launch("frhip_cast_to_f32");
+    return by_dtype(dtype, "frhip_cast_to_f32", [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(cast_to_f32_kernel<T>, dim3(grid_for(n, 256)), dim3(256), 0, stream, (const T*)src, dst, n);
+        return check_launch("frhip_cast_to_f32");
+    });
 }

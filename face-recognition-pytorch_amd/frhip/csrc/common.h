@@ -31,6 +31,16 @@ int check_launch(const char* what);
 int set_dynamic_lds(const void* fn, int bytes, const char* who);
 // Compute units of the current device, cached per device (256 when the runtime cannot say).
 int device_cu_count();
+// The one dtype dispatch of the host side: f(bf16_t{}) or f(float{}); any other dtype sets "<who>: bad dtype <d>" and returns
+// FRHIP_EINVAL before f runs.  f takes the element type from its tag (typedef decltype(t) T;) and returns the entry point's status.
+// Every entry point calls it before it reads another argument; one whose dispatch lies further down (tile choices that differ per
+// type, bf16-only kernels) calls it first with an f that only returns FRHIP_OK.
+template <typename F> int by_dtype(int dtype, const char* who, F&& f) {
+    if (dtype == FRHIP_DT_BF16) return f(bf16_t{});
+    if (dtype == FRHIP_DT_F32) return f(float{});
+    set_error("%s: bad dtype %d", who, dtype);
+    return FRHIP_EINVAL;
+}
 
 // ---- buffer resource (raw, stride 0).  OOB reads return 0 -- used for conv zero padding.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, uint32_t bytes) {

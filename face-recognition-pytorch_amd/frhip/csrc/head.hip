@@ -557,8 +557,8 @@ static int head_fwd_impl(const char* who, int dtype, const void* ehat, const voi
                          float* rowsum, hipStream_t stream) {
     NtGeom g;
     HeadMargin hm = {};
-    int rc = head_geom(g, dtype, n, classes, d, sub, K, who);
-    if (rc || (rc = margin_desc(margin, hm, who))) return rc;
+    int rc = by_dtype(dtype, who, [](auto) { return FRHIP_OK; });
+    if (rc || (rc = head_geom(g, dtype, n, classes, d, sub, K, who)) || (rc = margin_desc(margin, hm, who))) return rc;
     HeadArgs a = {};
     a.ehat = ehat; a.what = what; a.labels = labels; a.pmax = part_max; a.psum = part_sum; a.zt = ztarget; a.tsub = tsub;
     if ((rc = head_launch<true>(dtype, g, a, hm, sub ? K : 0, stream))) return rc;
@@ -575,8 +575,9 @@ static int head_bwd_dt_impl(const char* who, int dtype, const void* ehat, const 
                             const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt, hipStream_t stream) {
     NtGeom g;
     HeadMargin hm = {};
-    int rc = head_geom(g, dtype, n, classes, d, sub, K, who);
-    if (rc || (rc = head_pitches(dtype, n, classes, sub, K, ldt, ldp, dtt, ldtt, who)) || (rc = margin_desc(margin, hm, who))) return rc;
+    int rc = by_dtype(dtype, who, [](auto) { return FRHIP_OK; });
+    if (rc || (rc = head_geom(g, dtype, n, classes, d, sub, K, who)) ||
+        (rc = head_pitches(dtype, n, classes, sub, K, ldt, ldp, dtt, ldtt, who)) || (rc = margin_desc(margin, hm, who))) return rc;
     HeadArgs a = {};
     a.ehat = ehat; a.what = what; a.labels = labels; a.rmax = rowmax; a.rsum = rowsum; a.gscale = gscale; a.upstream = upstream;
     a.dt = dt; a.ldt = ldt; a.ldp = ldp; a.dtt = dtt; a.ldtt = ldtt;
@@ -646,7 +647,7 @@ extern "C" int frhip_head_groups(int num_classes) { return ((num_classes + 127) 
 extern "C" int frhip_head_fwd_ex(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
                                  int d, const frhip_margin_t* margin, float* part_max, float* part_sum, float* ztarget,
                                  float* rowmax, float* rowsum, hipStream_t stream) {
-    return head_fwd_impl("frhip_head_fwd", dtype, ehat, what, labels, n, classes, d, false, 1, margin, part_max, part_sum, ztarget, nullptr,
+    return head_fwd_impl("frhip_head_fwd_ex", dtype, ehat, what, labels, n, classes, d, false, 1, margin, part_max, part_sum, ztarget, nullptr,
                          rowmax, rowsum, stream);
 }
 
@@ -654,7 +655,8 @@ extern "C" int frhip_head_fwd(int dtype, const void* ehat, const void* what, con
                               int d, float s, float m, float* part_max, float* part_sum, float* ztarget,
                               float* rowmax, float* rowsum, hipStream_t stream) {
     const frhip_margin_t mg = {FRHIP_MARGIN_ARCFACE, 0, s, m, 0.f};
-    return frhip_head_fwd_ex(dtype, ehat, what, labels, n, classes, d, &mg, part_max, part_sum, ztarget, rowmax, rowsum, stream);
+    return head_fwd_impl("frhip_head_fwd", dtype, ehat, what, labels, n, classes, d, false, 1, &mg, part_max, part_sum, ztarget, nullptr,
+                         rowmax, rowsum, stream);
 }
 
 extern "C" int frhip_head_fwd_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
@@ -683,7 +685,7 @@ extern "C" int frhip_head_fwd_sub_rows(int dtype, const void* ehat, const void* 
 extern "C" int frhip_head_bwd_dt_ex(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
                                     int d, const frhip_margin_t* margin, const float* rowmax, const float* rowsum, float gscale,
                                     const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
-    return head_bwd_dt_impl("frhip_head_bwd_dt", dtype, ehat, what, labels, n, classes, d, false, 1, margin, rowmax, rowsum, gscale,
+    return head_bwd_dt_impl("frhip_head_bwd_dt_ex", dtype, ehat, what, labels, n, classes, d, false, 1, margin, rowmax, rowsum, gscale,
                             upstream, dt, ldt, 0, dtt, ldtt, stream);
 }
 
@@ -691,7 +693,8 @@ extern "C" int frhip_head_bwd_dt(int dtype, const void* ehat, const void* what, 
                                  int d, float s, float m, const float* rowmax, const float* rowsum, float gscale,
                                  const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
     const frhip_margin_t mg = {FRHIP_MARGIN_ARCFACE, 0, s, m, 0.f};
-    return frhip_head_bwd_dt_ex(dtype, ehat, what, labels, n, classes, d, &mg, rowmax, rowsum, gscale, upstream, dt, ldt, dtt, ldtt, stream);
+    return head_bwd_dt_impl("frhip_head_bwd_dt", dtype, ehat, what, labels, n, classes, d, false, 1, &mg, rowmax, rowsum, gscale,
+                            upstream, dt, ldt, 0, dtt, ldtt, stream);
 }
 
 extern "C" int frhip_head_bwd_dt_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
@@ -718,21 +721,23 @@ extern "C" int frhip_head_bwd_dt_sub_rows(int dtype, const void* ehat, const voi
 }
 extern "C" int frhip_l2norm_rows(int dtype, const float* x, void* xhat, float* norms, int rows, int d, float eps,
                                  hipStream_t stream) {
-    if (d % 4) { set_error("frhip_l2norm_rows: d must be a multiple of 4"); return FRHIP_EINVAL; }
-    if (dtype == FRHIP_DT_BF16 && d == 512) hipLaunchKernelGGL(l2norm_rows512_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, x, (bf16_t*)xhat, norms, rows, eps);
-    else if (dtype == FRHIP_DT_BF16) hipLaunchKernelGGL(l2norm_rows_kernel<bf16_t>, dim3((rows + 3) / 4), dim3(256), 0, stream, x, (bf16_t*)xhat, norms, rows, d, eps);
-    else if (dtype == FRHIP_DT_F32) hipLaunchKernelGGL(l2norm_rows_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, stream, x, (float*)xhat, norms, rows, d, eps);
-    else { set_error("frhip_l2norm_rows: bad dtype %d", dtype); return FRHIP_EINVAL; }
-    return check_launch("frhip_l2norm_rows");
+    return by_dtype(dtype, "frhip_l2norm_rows", [&](auto t) {
+        typedef decltype(t) T;
+        if (d % 4) { set_error("frhip_l2norm_rows: d must be a multiple of 4"); return FRHIP_EINVAL; }
+        if (dtype == FRHIP_DT_BF16 && d == 512) hipLaunchKernelGGL(l2norm_rows512_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, x, (bf16_t*)xhat, norms, rows, eps);
+        else hipLaunchKernelGGL(l2norm_rows_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, stream, x, (T*)xhat, norms, rows, d, eps);
+        return check_launch("frhip_l2norm_rows");
+    });
 }
 
 extern "C" int frhip_l2norm_bwd(int dtype, const float* dxhat, const void* xhat, const float* norms, float* dx,
                                 int rows, int d, float out_scale, hipStream_t stream) {
-    if (dtype == FRHIP_DT_BF16 && d == 512) hipLaunchKernelGGL(l2norm_bwd512_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, dxhat, (const bf16_t*)xhat, norms, dx, rows, out_scale);
-    else if (dtype == FRHIP_DT_BF16) hipLaunchKernelGGL(l2norm_bwd_kernel<bf16_t>, dim3((rows + 3) / 4), dim3(256), 0, stream, dxhat, (const bf16_t*)xhat, norms, dx, rows, d, out_scale);
-    else if (dtype == FRHIP_DT_F32) hipLaunchKernelGGL(l2norm_bwd_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, stream, dxhat, (const float*)xhat, norms, dx, rows, d, out_scale);
-    else { set_error("frhip_l2norm_bwd: bad dtype %d", dtype); return FRHIP_EINVAL; }
-    return check_launch("frhip_l2norm_bwd");
+    return by_dtype(dtype, "frhip_l2norm_bwd", [&](auto t) {
+        typedef decltype(t) T;
+        if (dtype == FRHIP_DT_BF16 && d == 512) hipLaunchKernelGGL(l2norm_bwd512_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, dxhat, (const bf16_t*)xhat, norms, dx, rows, out_scale);
+        else hipLaunchKernelGGL(l2norm_bwd_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, stream, dxhat, (const T*)xhat, norms, dx, rows, d, out_scale);
+        return check_launch("frhip_l2norm_bwd");
+    });
 }
 
 extern "C" int frhip_head_rescale(float* rowsum, const float* local_max, const float* global_max, int n, hipStream_t stream) {

@@ -309,18 +309,20 @@ extern "C" int frhip_quant_fp8_weights_multi(const frhip_q8w* table, int ntensor
 }
 
 extern "C" int frhip_quant_fp8(int dtype, const void* x, void* x8, size_t n, float inv_scale, hipStream_t stream) {
-    if (n % 16) { set_error("frhip_quant_fp8: n must be a multiple of 16"); return FRHIP_EINVAL; }
-    const size_t n16 = n / 16;
-    const unsigned grid = (unsigned)((n16 + 255) / 256 > 65536 ? 65536 : (n16 + 255) / 256);
-    if (dtype == FRHIP_DT_BF16) hipLaunchKernelGGL(quant_act8_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, (const bf16_t*)x, (uint8_t*)x8, n16, inv_scale, g_fp8_sat_ptr);
-    else if (dtype == FRHIP_DT_F32) hipLaunchKernelGGL(quant_act8_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)x, (uint8_t*)x8, n16, inv_scale, g_fp8_sat_ptr);
-    else { set_error("frhip_quant_fp8: bad dtype %d", dtype); return FRHIP_EINVAL; }
-    return check_launch("frhip_quant_fp8");
+    return by_dtype(dtype, "frhip_quant_fp8", [&](auto t) {
+        typedef decltype(t) T;
+        if (n % 16) { set_error("frhip_quant_fp8: n must be a multiple of 16"); return FRHIP_EINVAL; }
+        const size_t n16 = n / 16;
+        const unsigned grid = (unsigned)((n16 + 255) / 256 > 65536 ? 65536 : (n16 + 255) / 256);
+        hipLaunchKernelGGL(quant_act8_kernel<T>, dim3(grid), dim3(256), 0, stream, (const T*)x, (uint8_t*)x8, n16, inv_scale, g_fp8_sat_ptr);
+        return check_launch("frhip_quant_fp8");
+    });
 }
 
 extern "C" int frhip_bn_apply_q8(int dtype, const void* y, const float* scale, const float* shift, const void* res,
                                  const float* res_scale, const float* res_shift, int relu, void* out, void* out8, float inv_q,
                                  int rows, int c, hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_bn_apply_q8", [](auto) { return FRHIP_OK; })) return rc;
     const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
     if (dtype != FRHIP_DT_BF16 || c % epv || c / epv > 256 || 256 % (c / epv) || !out8) {
         set_error("frhip_bn_apply_q8: bf16 only, c/8 must divide 256 (c=%d)", c);

@@ -224,13 +224,12 @@ int halo_run(int dtype, const void* a, const void* b, void* out, const void* res
         return halo_launch<bf16_t, 4, 1, 4, 1, true>(g, a, b, out, res, stats, br, stream);
     }
     if (halo_config_w(dtype, w, c, k, sign) == 3) return halo_wide_launch(g, a, b, out, res, stats, br, stream);
-    if (dtype == FRHIP_DT_BF16) {
-        if (cfg == 0) return halo_launch<bf16_t, 4, 1, 4, 1>(g, a, b, out, res, stats, br, stream);
-        if (cfg == 1) return halo_launch<bf16_t, 8, 1, 2, 2>(g, a, b, out, res, stats, br, stream);
-        return halo_launch<bf16_t, 4, 2, 4, 2>(g, a, b, out, res, stats, br, stream);
-    }
-    if (cfg == 1) return halo_launch<float, 8, 1, 2, 2>(g, a, b, out, res, stats, br, stream);
-    return halo_launch<float, 4, 2, 4, 2>(g, a, b, out, res, stats, br, stream);
+    if (dtype == FRHIP_DT_BF16 && cfg == 0) return halo_launch<bf16_t, 4, 1, 4, 1>(g, a, b, out, res, stats, br, stream);   // bf16 only
+    return by_dtype(dtype, "igemm_halo", [&](auto t) {
+        typedef decltype(t) T;
+        return cfg == 1 ? halo_launch<T, 8, 1, 2, 2>(g, a, b, out, res, stats, br, stream)
+                        : halo_launch<T, 4, 2, 4, 2>(g, a, b, out, res, stats, br, stream);
+    });
 }
 
 }  // namespace frhip

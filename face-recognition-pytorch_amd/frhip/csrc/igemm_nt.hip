@@ -142,26 +142,18 @@ static int nt_dispatch(int dtype, const NtGeom& g, const void* a, const void* b,
 #define NT_GO(T, WM, WN, MT)                                                                              \
     return atomic ? nt_launch_cfg<T, WM, WN, MT, EPI_ATOMIC>(g, a, b, out, res, stats, br, splits, stream)     \
                   : nt_launch_cfg<T, WM, WN, MT, EPI_STORE>(g, a, b, out, res, stats, br, splits, stream)
-    if (dtype == FRHIP_DT_BF16) {
-        switch (tile) {
-            case 2: NT_GO(bf16_t, 4, 1, 4);
-            case 3: NT_GO(bf16_t, 4, 2, 4);
-            case 4: if (!atomic && splits == 1 && g_epi_lean && nt_lean_ok(true, g.M, g.Nout, br, stats))
-                        return nt_launch_cfg<bf16_t, 2, 4, 8, EPI_LEAN>(g, a, b, out, res, stats, br, splits, stream);
-                    if (!atomic) return nt_launch_cfg<bf16_t, 2, 4, 8, EPI_STORE>(g, a, b, out, res, stats, br, splits, stream);
-                    NT_GO(bf16_t, 4, 2, 4);
-            default: NT_GO(bf16_t, 2, 2, 4);
-        }
+    if (dtype == FRHIP_DT_BF16 && (tile == 3 || tile == 4)) {     // the two tiles that fp32 lacks (nt_pick_tile never names them for fp32)
+        if (tile == 4 && !atomic && splits == 1 && g_epi_lean && nt_lean_ok(true, g.M, g.Nout, br, stats))
+            return nt_launch_cfg<bf16_t, 2, 4, 8, EPI_LEAN>(g, a, b, out, res, stats, br, splits, stream);
+        if (tile == 4 && !atomic) return nt_launch_cfg<bf16_t, 2, 4, 8, EPI_STORE>(g, a, b, out, res, stats, br, splits, stream);
+        NT_GO(bf16_t, 4, 2, 4);
     }
-    if (dtype == FRHIP_DT_F32) {
-        switch (tile) {
-            case 2: NT_GO(float, 4, 1, 4);
-            default: NT_GO(float, 2, 2, 4);
-        }
-    }
+    return by_dtype(dtype, "igemm_nt", [&](auto t) {
+        typedef decltype(t) T;
+        if (tile == 2) NT_GO(T, 4, 1, 4);
+        NT_GO(T, 2, 2, 4);
+    });
 #undef NT_GO
-    set_error("igemm_nt: bad dtype %d", dtype);
-    return FRHIP_EINVAL;
 }
 
 static int esize(int dtype) { return dtype == FRHIP_DT_BF16 ? 2 : 4; }
@@ -232,6 +224,7 @@ extern "C" int frhip_set_nt_tile(int tile) { const int old = g_nt_tile; g_nt_til
 extern "C" int frhip_conv_fwd(int dtype, const void* x, const void* w, void* y, float* stats_partial,
                               int n, int h, int wd, int c, int k, int r, int s, int stride, int pad,
                               hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_conv_fwd", [](auto) { return FRHIP_OK; })) return rc;
     NtGeom g;
     const int ho = (h + 2 * pad - r) / stride + 1, wo = (wd + 2 * pad - s) / stride + 1;
     int rc = fill_geom(g, dtype, n, h, wd, c, ho, wo, k, r, s, stride, pad, 0, "frhip_conv_fwd");
@@ -244,6 +237,7 @@ extern "C" int frhip_conv_fwd(int dtype, const void* x, const void* w, void* y, 
 extern "C" int frhip_conv_fwd_affine(int dtype, const void* x, const void* w, void* y, const float* scale, const float* shift, int relu,
                                      const void* residual, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad,
                                      hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_conv_fwd_affine", [](auto) { return FRHIP_OK; })) return rc;
     // y = [relu](conv(x, w) * scale[k] + shift[k] + residual): eval-mode BatchNorm (frhip_bn_eval_affine) folded into the store epilogue
     if (!scale || !shift) { set_error("frhip_conv_fwd_affine: scale and shift are required"); return FRHIP_EINVAL; }
     NtGeom g;
@@ -269,6 +263,7 @@ extern "C" int frhip_conv_bnrelu_fusable(int dtype, int h, int wd, int c, int k,
 extern "C" int frhip_conv_fwd_bnrelu(int dtype, const void* x, const float* in_scale, const float* in_shift, const void* w, void* y,
                                      float* stats_partial, void* act_out, int n, int h, int wd, int c, int k, int r, int s, int stride,
                                      int pad, hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_conv_fwd_bnrelu", [](auto) { return FRHIP_OK; })) return rc;
     // y = conv(relu(x * in_scale[c] + in_shift[c]), w): BatchNorm-apply + ReLU of the operand inside the kernel (bn1 -> relu -> conv2);
     // act_out (optional, shaped like x): the activated tensor, written on the way for the backward pass
     if (!in_scale || !in_shift || !halo_xf_applicable(dtype, h, wd, c, k, r, s, stride, pad)) {
@@ -305,6 +300,7 @@ static int dgrad_run(int dtype, const void* dy, const void* wt, void* dx, const 
 extern "C" int frhip_conv_dgrad(int dtype, const void* dy, const void* wt, void* dx, const void* residual,
                                 int n, int h, int wd, int c, int k, int r, int s, int stride, int pad,
                                 hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_conv_dgrad", [](auto) { return FRHIP_OK; })) return rc;
     return dgrad_run(dtype, dy, wt, dx, residual, nullptr, NO_BNRED, n, h, wd, c, k, r, s, stride, pad, stream, "frhip_conv_dgrad");
 }
 
@@ -330,6 +326,7 @@ extern "C" int frhip_conv_dgrad_fused(int dtype, const void* dy, const void* wt,
                                       int residual_stride, const void* y_bn, const float* mean, const float* invstd,
                                       const float* mask_scale, const float* mask_shift, float* stats_partial, int n, int h,
                                       int wd, int c, int k, int r, int s, int stride, int pad, hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_conv_dgrad_fused", [](auto) { return FRHIP_OK; })) return rc;
     if (residual_stride != 1 && residual_stride != 2) { set_error("frhip_conv_dgrad_fused: residual_stride must be 1 or 2"); return FRHIP_EINVAL; }
     if (y_bn && (!mean || !invstd || !stats_partial || (mask_scale && !mask_shift))) {
         set_error("frhip_conv_dgrad_fused: y_bn needs mean, invstd and stats_partial");
@@ -346,6 +343,7 @@ extern "C" int frhip_conv_dgrad_fused_rs(int dtype, const void* dy, const void* 
                                          const float* mask_scale, const float* mask_shift, const float* rowscale, int rows_per,
                                          float keep_scale, float* stats_partial, int n, int h, int wd, int c, int k, int r, int s,
                                          int stride, int pad, hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_conv_dgrad_fused_rs", [](auto) { return FRHIP_OK; })) return rc;
     // frhip_conv_dgrad_fused whose BatchNorm sits under stochastic depth: the sums describe dx * rowscale[row / rows_per]
     if (residual_stride != 1 && residual_stride != 2) { set_error("frhip_conv_dgrad_fused_rs: residual_stride must be 1 or 2"); return FRHIP_EINVAL; }
     if (!y_bn || !mean || !invstd || !stats_partial || (mask_scale && !mask_shift) || !rowscale || rows_per <= 0 ||
@@ -363,6 +361,7 @@ extern "C" int frhip_conv_dgrad_bnred(int dtype, const void* dy, const void* wt,
                                       const void* y_bn, const float* mean, const float* invstd, const float* mask_scale,
                                       const float* mask_shift, float* stats_partial, int n, int h, int wd, int c, int k,
                                       int r, int s, int stride, int pad, hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_conv_dgrad_bnred", [](auto) { return FRHIP_OK; })) return rc;
     if (!y_bn || !mean || !invstd || !stats_partial || (mask_scale && !mask_shift)) {
         set_error("frhip_conv_dgrad_bnred: y_bn, mean, invstd and stats_partial are required");
         return FRHIP_EINVAL;
@@ -373,6 +372,7 @@ extern "C" int frhip_conv_dgrad_bnred(int dtype, const void* dy, const void* wt,
 
 extern "C" int frhip_linear_fwd(int dtype, const void* a, const void* w, const float* bias, void* out, void* act_out,
                                 float* stats_partial, int m, int n, int k, hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_linear_fwd", [](auto) { return FRHIP_OK; })) return rc;
     // out[m][n] = sum_k a[m][k] * w[n][k] + bias[n]; act_out = gelu(out); stats_partial as frhip_conv_fwd (a 1x1 conv)
     NtGeom g;
     int rc = fill_geom(g, dtype, m, 1, 1, k, 1, 1, n, 1, 1, 1, 0, 0, "frhip_linear_fwd");
@@ -384,6 +384,7 @@ extern "C" int frhip_linear_fwd(int dtype, const void* a, const void* w, const f
 
 extern "C" int frhip_linear_dgrad_gelu(int dtype, const void* dy, const void* wt, const void* pre, void* dx,
                                        float* stats_partial, int m, int n, int k, hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_linear_dgrad_gelu", [](auto) { return FRHIP_OK; })) return rc;
     // dx[m][n] = (sum_k dy[m][k] * wt[n][k]) * gelu'(pre[m][n]); stats_partial[.][0][n] sums to the column sums of dx
     if (!pre) { set_error("frhip_linear_dgrad_gelu: the saved pre-activation is required"); return FRHIP_EINVAL; }
     NtGeom g;
@@ -409,28 +410,29 @@ __global__ __launch_bounds__(256) void nt_slab_reduce_kernel(const float* __rest
 
 extern "C" int frhip_gemm_nt_splitk(int dtype, const void* a, const void* b, const float* bias, float* out, int m, int n,
                                     int k, int splits, float* slabs, size_t slab_bytes, hipStream_t stream) {
-    // out[m][n] fp32 = sum_k a[m][k] * b[n][k] + bias[n]: K split `splits` ways, every split stores a private fp32 slab
-    // (plain stores), one pass adds the slabs in split order -> run-to-run identical (no float atomics)
-    NtGeom g;
-    int rc = fill_geom(g, dtype, m, 1, 1, k, 1, 1, n, 1, 1, 1, 0, 0, "frhip_gemm_nt_splitk");
-    if (rc) return rc;
-    if (n % 4) { set_error("frhip_gemm_nt_splitk: n must be a multiple of 4"); return FRHIP_EINVAL; }
-    if (splits < 1) splits = 1;
-    if (splits > g.ksteps) splits = g.ksteps;
-    g.ksteps_per_split = (g.ksteps + splits - 1) / splits;
-    splits = (g.ksteps + g.ksteps_per_split - 1) / g.ksteps_per_split;
-    const size_t elems = (size_t)m * n;
-    if (!slabs || slab_bytes < elems * 4 * (size_t)splits) { set_error("frhip_gemm_nt_splitk: workspace too small (%zu bytes needed)", elems * 4 * (size_t)splits); return FRHIP_EINVAL; }
-    if (dtype == FRHIP_DT_BF16) rc = nt_launch_cfg<bf16_t, 2, 2, 4, EPI_SLAB>(g, a, b, slabs, nullptr, nullptr, NO_BNRED, splits, stream);
-    else if (dtype == FRHIP_DT_F32) rc = nt_launch_cfg<float, 2, 2, 4, EPI_SLAB>(g, a, b, slabs, nullptr, nullptr, NO_BNRED, splits, stream);
-    else { set_error("frhip_gemm_nt_splitk: bad dtype %d", dtype); return FRHIP_EINVAL; }
-    if (rc) return rc;
-    hipLaunchKernelGGL(nt_slab_reduce_kernel, dim3((unsigned)((elems / 4 + 255) / 256)), dim3(256), 0, stream, slabs, splits, elems, bias, n, out);
-    return check_launch("frhip_gemm_nt_splitk/reduce");
+    return by_dtype(dtype, "frhip_gemm_nt_splitk", [&](auto t) {
+        // out[m][n] fp32 = sum_k a[m][k] * b[n][k] + bias[n]: K split `splits` ways, every split stores a private fp32 slab
+        // (plain stores), one pass adds the slabs in split order -> run-to-run identical (no float atomics)
+        NtGeom g;
+        int rc = fill_geom(g, dtype, m, 1, 1, k, 1, 1, n, 1, 1, 1, 0, 0, "frhip_gemm_nt_splitk");
+        if (rc) return rc;
+        if (n % 4) { set_error("frhip_gemm_nt_splitk: n must be a multiple of 4"); return FRHIP_EINVAL; }
+        if (splits < 1) splits = 1;
+        if (splits > g.ksteps) splits = g.ksteps;
+        g.ksteps_per_split = (g.ksteps + splits - 1) / splits;
+        splits = (g.ksteps + g.ksteps_per_split - 1) / g.ksteps_per_split;
+        const size_t elems = (size_t)m * n;
+        if (!slabs || slab_bytes < elems * 4 * (size_t)splits) { set_error("frhip_gemm_nt_splitk: workspace too small (%zu bytes needed)", elems * 4 * (size_t)splits); return FRHIP_EINVAL; }
+        rc = nt_launch_cfg<decltype(t), 2, 2, 4, EPI_SLAB>(g, a, b, slabs, nullptr, nullptr, NO_BNRED, splits, stream);
+        if (rc) return rc;
+        hipLaunchKernelGGL(nt_slab_reduce_kernel, dim3((unsigned)((elems / 4 + 255) / 256)), dim3(256), 0, stream, slabs, splits, elems, bias, n, out);
+        return check_launch("frhip_gemm_nt_splitk/reduce");
+    });
 }
 
 extern "C" int frhip_gemm_nt(int dtype, const void* a, const void* b, void* out, int m, int n, int k,
                              int splits, int atomic_f32, hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_gemm_nt", [](auto) { return FRHIP_OK; })) return rc;
     // out[m][n] = sum_k a[m][k] * b[n][k].  atomic_f32 == 0: out has dtype and is overwritten;
     // atomic_f32 == 1: out is fp32, zeroed by the caller, K is split and partial sums are added atomically.
     NtGeom g;

@@ -10,6 +10,7 @@
 // adds its tiles into the output directly, in whole 256-byte rows staged through LDS.
 // Reference counterpart: autograd of nn.Conv2d / F.linear (cuDNN wgrad), nets/resnet.py:23-46, nets/PartialFC.py:201.
 #include "common.h"
+#include "tr_frag.h"
 #include "frhip.h"
 
 namespace frhip {
@@ -48,10 +49,6 @@ struct TnGeom {
 constexpr int TN_THREADS = 256;
 constexpr int TN_KP = 64;   // pixels per K step
 
-template <int RB> __device__ __forceinline__ int tn_swz(int row);
-template <> __device__ __forceinline__ int tn_swz<256>(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-template <> __device__ __forceinline__ int tn_swz<128>(int row) { return (((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 1; }
-
 template <typename T, int RB>
 struct TnTile {
     static constexpr int BC = RB / (int)sizeof(T);        // channels per tile side
@@ -64,40 +61,6 @@ struct TnTile {
     static constexpr int PIECES = TN_KP / ROWS_PER_PIECE / 4;   // per wave per tile: 4 or 2
     static constexpr int OUT_PITCH = WC * 4 + 16;
     static constexpr int LDS_BYTES = (2 * STAGE_BYTES > 4 * WC * OUT_PITCH) ? 2 * STAGE_BYTES : 4 * WC * OUT_PITCH;
-};
-
-// fragment for one MFMA K group from a [pixel][channel] LDS tile, channels c0..c0+15, pixel rows r0 + (k slots)
-template <typename T, int RB> struct TnFrag;
-template <int RB> struct TnFrag<bf16_t, RB> {
-    // 32 pixels per MFMA: lane group g covers pixels r0 + 8g .. 8g+7 via two transposed 4x16 block reads
-    static constexpr int KROWS = 32;
-    __device__ static __forceinline__ bf16x8_t load(const char* tile, int r0, int c0, int lane) {
-        const int g = lane >> 4, j = lane & 15, q = j >> 2, p = j & 3;
-        const int chunk = (c0 >> 3) + (p >> 1);
-        const int row_a = r0 + 8 * g + q, row_b = row_a + 4;
-        const char* pa = tile + row_a * RB + ((chunk ^ tn_swz<RB>(row_a)) << 4) + 8 * (p & 1);
-        const char* pb = tile + row_b * RB + ((chunk ^ tn_swz<RB>(row_b)) << 4) + 8 * (p & 1);
-        i16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4_t*)LDS_ADDR(pa));
-        i16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4_t*)LDS_ADDR(pb));
-        typedef __attribute__((ext_vector_type(8))) short i16x8_t;
-        i16x8_t v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(bf16x8_t, v);
-    }
-};
-template <int RB> struct TnFrag<float, RB> {
-    // 16 pixels per "K group" (4 MFMA 16x16x4): element e of lane group g is pixel r0 + 4e + g
-    static constexpr int KROWS = 16;
-    __device__ static __forceinline__ f32x4_t load(const char* tile, int r0, int c0, int lane) {
-        const int g = lane >> 4, i = lane & 15;
-        const int col = c0 + i, chunk = col >> 2, within = (col & 3) * 4;
-        f32x4_t v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int row = r0 + 4 * e + g;
-            v[e] = *reinterpret_cast<const float*>(tile + row * RB + ((chunk ^ tn_swz<RB>(row)) << 4) + within);
-        }
-        return v;
-    }
 };
 
 template <typename T, int RB, int NT>
@@ -1088,8 +1051,8 @@ static int r14_plan(TnGeom& g, int n, int splits) {
 static int tn_run(int dtype, const void* p, const void* q, float* out, int n, int h, int w, int c, int kc, int ldp,
                   int r, int s, int stride, int pad, int splits, float* ws, size_t ws_bytes, hipStream_t stream,
                   const char* who, bool overwrite = false, const float* xf_scale = nullptr, const float* xf_shift = nullptr) {
+    if (const int rc = by_dtype(dtype, who, [](auto) { return FRHIP_OK; })) return rc;
     const int es = dtype == FRHIP_DT_BF16 ? 2 : 4;
-    if (dtype != FRHIP_DT_BF16 && dtype != FRHIP_DT_F32) { set_error("%s: bad dtype %d", who, dtype); return FRHIP_EINVAL; }
     const int epv = 16 / es;
     if (n <= 0 || c <= 0 || kc <= 0 || (c % epv) || (ldp % epv) || ldp < kc) {
         set_error("%s: unsupported shape c=%d kc=%d ldp=%d (c and ldp must be multiples of %d, ldp >= kc)", who, c, kc, ldp, epv);
@@ -1189,18 +1152,20 @@ static int tn_run(int dtype, const void* p, const void* q, float* out, int n, in
         // out = result (not +=) and a single K split: the "slab" store path with slab 0 = out itself -- plain coalesced stores,
         // no zero fill by the caller and no fp32 atomic read-modify-write pass over the output (the head's 250-MB dW)
         g.slab_stride = (int)out_elems;
-        if (dtype == FRHIP_DT_BF16) return big ? tn_launch<bf16_t, 256>(g, p, q, out, taps, 1, stream) : tn_launch<bf16_t, 128>(g, p, q, out, taps, 1, stream);
-        return big ? tn_launch<float, 256>(g, p, q, out, taps, 1, stream) : tn_launch<float, 128>(g, p, q, out, taps, 1, stream);
+        return by_dtype(dtype, who, [&](auto t) {
+            typedef decltype(t) T;
+            return big ? tn_launch<T, 256>(g, p, q, out, taps, 1, stream) : tn_launch<T, 128>(g, p, q, out, taps, 1, stream);
+        });
     }
     if (overwrite && hipMemsetAsync(out, 0, out_elems * sizeof(float), stream) != hipSuccess) {
         set_error("%s: cannot clear the output", who);
         return FRHIP_ELAUNCH;
     }
     float* dst = tn_pick_dst(g, out, splits, out_elems, ws, ws_bytes);
-    if (dtype == FRHIP_DT_BF16) rc = big ? tn_launch<bf16_t, 256>(g, p, q, dst, taps, splits, stream)
-                                              : tn_launch<bf16_t, 128>(g, p, q, dst, taps, splits, stream);
-    else rc = big ? tn_launch<float, 256>(g, p, q, dst, taps, splits, stream)
-                  : tn_launch<float, 128>(g, p, q, dst, taps, splits, stream);
+    rc = by_dtype(dtype, who, [&](auto t) {
+        typedef decltype(t) T;
+        return big ? tn_launch<T, 256>(g, p, q, dst, taps, splits, stream) : tn_launch<T, 128>(g, p, q, dst, taps, splits, stream);
+    });
     return rc ? rc : tn_finish(g, out, splits, out_elems, ws, stream);
 }
 
@@ -1356,6 +1321,7 @@ extern "C" int frhip_conv_wgrad_chain_ok(int dtype, int n, int h, int w, int c, 
 extern "C" int frhip_conv_wgrad_chain(int dtype, const void* dy, const void* x, int n, int h, int w, int c, int k,
                                       float* slabs, size_t slab_bytes, float* prev_dw, const float* prev_slabs, int prev_k, int prev_c,
                                       int prev_splits, int* splits_out, hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_conv_wgrad_chain", [](auto) { return FRHIP_OK; })) return rc;
     if (!frhip_conv_wgrad_chain_ok(dtype, n, h, w, c, k, 3, 3, 1, 1) || !slabs || !splits_out) {
         set_error("frhip_conv_wgrad_chain: shape not served by the rows kernel (bf16 3x3 stride 1 on 14 x 14 maps, c and k multiples of 64, n >= 2)");
         return FRHIP_EINVAL;
@@ -1396,6 +1362,7 @@ extern "C" int frhip_head_dw_ok(int dtype, int n, int classes, int d) {
 
 extern "C" int frhip_head_dw(int dtype, const void* dt, int ldt, const void* ehat, const void* what, const float* wnorm, float* dw,
                              int n, int classes, int d, float out_scale, hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_head_dw", [](auto) { return FRHIP_OK; })) return rc;
     if (!frhip_head_dw_ok(dtype, n, classes, d) || !dt || !ehat || !what || !wnorm || !dw || ldt < classes || (ldt % 8) ||
         (long long)n * ldt * 2 >= 0x7fffffffLL) {
         set_error("frhip_head_dw: bf16, d == 512, ldt >= classes in whole eights and dT below 2 GiB are required");
@@ -1427,6 +1394,7 @@ extern "C" int frhip_conv_wgrad_bnrelu(int dtype, const void* dy, const void* x,
                                        float* workspace, size_t workspace_bytes, hipStream_t stream) {
     // dw += wgrad(dy, relu(x * in_scale[c] + in_shift[c])): weight gradient of the convolution behind a BatchNorm + ReLU whose
     // output was never materialised (frhip_conv_fwd_bnrelu); the activation is re-formed in LDS from the saved BatchNorm input
+    if (const int rc = by_dtype(dtype, "frhip_conv_wgrad_bnrelu", [](auto) { return FRHIP_OK; })) return rc;
     if (!in_scale || !in_shift) { frhip::set_error("frhip_conv_wgrad_bnrelu: scale / shift required"); return FRHIP_EINVAL; }
     return tn_run(dtype, dy, x, dw, n, h, w, c, k, k, r, s, stride, pad, splits, workspace, workspace_bytes, stream,
                   "frhip_conv_wgrad_bnrelu", false, in_scale, in_shift);

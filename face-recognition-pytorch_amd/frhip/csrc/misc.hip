@@ -205,20 +205,22 @@ extern "C" const char* frhip_last_error(void) { return g_err; }
 extern "C" int frhip_abi_version(void) { return 1; }
 
 extern "C" int frhip_pack_wt(int dtype, const float* w, void* wt, int k, int rs, int c, hipStream_t stream) {
-    dim3 grid((c + 31) / 32, (k + 31) / 32, rs), block(32, 8);
-    if (dtype == FRHIP_DT_BF16) hipLaunchKernelGGL(pack_wt_kernel<bf16_t>, grid, block, 0, stream, w, (bf16_t*)wt, k, rs, c);
-    else if (dtype == FRHIP_DT_F32) hipLaunchKernelGGL(pack_wt_kernel<float>, grid, block, 0, stream, w, (float*)wt, k, rs, c);
-    else { set_error("frhip_pack_wt: bad dtype %d", dtype); return FRHIP_EINVAL; }
-    return check_launch("frhip_pack_wt");
+    return by_dtype(dtype, "frhip_pack_wt", [&](auto t) {
+        typedef decltype(t) T;
+        dim3 grid((c + 31) / 32, (k + 31) / 32, rs), block(32, 8);
+        hipLaunchKernelGGL(pack_wt_kernel<T>, grid, block, 0, stream, w, (T*)wt, k, rs, c);
+        return check_launch("frhip_pack_wt");
+    });
 }
 
 extern "C" int frhip_prep_conv_weights(int dtype, const frhip_wprep* table, int ntensors, int ntiles, hipStream_t stream) {
-    if (!table || ntensors < 1 || ntiles < 1) { set_error("frhip_prep_conv_weights: empty table"); return FRHIP_EINVAL; }
-    dim3 block(32, 8);
-    if (dtype == FRHIP_DT_BF16) hipLaunchKernelGGL(prep_weights_kernel<bf16_t>, dim3(ntiles), block, 0, stream, table, ntensors);
-    else if (dtype == FRHIP_DT_F32) hipLaunchKernelGGL(prep_weights_kernel<float>, dim3(ntiles), block, 0, stream, table, ntensors);
-    else { set_error("frhip_prep_conv_weights: bad dtype %d", dtype); return FRHIP_EINVAL; }
-    return check_launch("frhip_prep_conv_weights");
+    return by_dtype(dtype, "frhip_prep_conv_weights", [&](auto t) {
+        typedef decltype(t) T;
+        if (!table || ntensors < 1 || ntiles < 1) { set_error("frhip_prep_conv_weights: empty table"); return FRHIP_EINVAL; }
+        dim3 block(32, 8);
+        hipLaunchKernelGGL(prep_weights_kernel<T>, dim3(ntiles), block, 0, stream, table, ntensors);
+        return check_launch("frhip_prep_conv_weights");
+    });
 }
 
 extern "C" int frhip_transpose2d(int dtype_in, int dtype_out, const void* in, void* out, int rows, int cols, int ld_out, hipStream_t stream) {
@@ -237,11 +239,12 @@ extern "C" int frhip_transpose2d(int dtype_in, int dtype_out, const void* in, vo
 }
 
 extern "C" int frhip_pack_stem(int dtype, const float* w, void* wp, int k, int kin, int kp, hipStream_t stream) {
-    const int n = k * kp;
-    if (dtype == FRHIP_DT_BF16) hipLaunchKernelGGL(pack_stem_kernel<bf16_t>, dim3((n + 255) / 256), dim3(256), 0, stream, w, (bf16_t*)wp, k, kin, kp);
-    else if (dtype == FRHIP_DT_F32) hipLaunchKernelGGL(pack_stem_kernel<float>, dim3((n + 255) / 256), dim3(256), 0, stream, w, (float*)wp, k, kin, kp);
-    else { set_error("frhip_pack_stem: bad dtype %d", dtype); return FRHIP_EINVAL; }
-    return check_launch("frhip_pack_stem");
+    return by_dtype(dtype, "frhip_pack_stem", [&](auto t) {
+        typedef decltype(t) T;
+        const int n = k * kp;
+        hipLaunchKernelGGL(pack_stem_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, stream, w, (T*)wp, k, kin, kp);
+        return check_launch("frhip_pack_stem");
+    });
 }
 
 extern "C" int frhip_unpack_stem_grad(const float* dwp, float* dw, int k, int kin, int kp, hipStream_t stream) {
@@ -251,13 +254,14 @@ extern "C" int frhip_unpack_stem_grad(const float* dwp, float* dw, int k, int ki
 }
 
 extern "C" int frhip_fc_permute(int dtype, const float* w, void* wp, int nout, int c, int hw, hipStream_t stream) {
-    if (c % 64) { set_error("frhip_fc_permute: channels must be a multiple of 64"); return FRHIP_EINVAL; }
-    dim3 grid(nout, c / 64);
-    const int lds = 64 * hw * 4;
-    if (dtype == FRHIP_DT_BF16) hipLaunchKernelGGL(fc_permute_kernel<bf16_t>, grid, dim3(256), lds, stream, w, (bf16_t*)wp, c, hw);
-    else if (dtype == FRHIP_DT_F32) hipLaunchKernelGGL(fc_permute_kernel<float>, grid, dim3(256), lds, stream, w, (float*)wp, c, hw);
-    else { set_error("frhip_fc_permute: bad dtype %d", dtype); return FRHIP_EINVAL; }
-    return check_launch("frhip_fc_permute");
+    return by_dtype(dtype, "frhip_fc_permute", [&](auto t) {
+        typedef decltype(t) T;
+        if (c % 64) { set_error("frhip_fc_permute: channels must be a multiple of 64"); return FRHIP_EINVAL; }
+        dim3 grid(nout, c / 64);
+        const int lds = 64 * hw * 4;
+        hipLaunchKernelGGL(fc_permute_kernel<T>, grid, dim3(256), lds, stream, w, (T*)wp, c, hw);
+        return check_launch("frhip_fc_permute");
+    });
 }
 
 extern "C" int frhip_fc_unpermute_grad(const float* dwp, float* dw, int nout, int c, int hw, hipStream_t stream) {

@@ -121,41 +121,38 @@ static int stem_grid(size_t total) {
 using namespace frhip;
 
 extern "C" int frhip_stem_im2col(int dtype, const float* x, void* col, int b, int h, int w, int stride, hipStream_t stream) {
-    if (stride != 1 && stride != 2) { set_error("frhip_stem_im2col: stride must be 1 or 2"); return FRHIP_EINVAL; }
-    const size_t total = (size_t)b * ((h - 1) / stride + 1) * ((w - 1) / stride + 1) * 8;
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL(stem_im2col_kernel<bf16_t>, dim3(stem_grid(total)), dim3(256), 0, stream, x, (bf16_t*)col, b, h, w, stride);
-    else if (dtype == FRHIP_DT_F32)
-        hipLaunchKernelGGL(stem_im2col_kernel<float>, dim3(stem_grid(total)), dim3(256), 0, stream, x, (float*)col, b, h, w, stride);
-    else { set_error("frhip_stem_im2col: bad dtype %d", dtype); return FRHIP_EINVAL; }
-    return check_launch("frhip_stem_im2col");
+    return by_dtype(dtype, "frhip_stem_im2col", [&](auto t) {
+        typedef decltype(t) T;
+        if (stride != 1 && stride != 2) { set_error("frhip_stem_im2col: stride must be 1 or 2"); return FRHIP_EINVAL; }
+        const size_t total = (size_t)b * ((h - 1) / stride + 1) * ((w - 1) / stride + 1) * 8;
+        hipLaunchKernelGGL(stem_im2col_kernel<T>, dim3(stem_grid(total)), dim3(256), 0, stream, x, (T*)col, b, h, w, stride);
+        return check_launch("frhip_stem_im2col");
+    });
 }
 
 extern "C" int frhip_bn_relu_maxpool_fwd(int dtype, const void* y, const float* scale, const float* shift, void* out,
                                          uint8_t* argmax, int b, int h, int w, int c, hipStream_t stream) {
-    const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
-    if ((dtype != FRHIP_DT_BF16 && dtype != FRHIP_DT_F32) || (c % epv)) { set_error("frhip_bn_relu_maxpool_fwd: bad dtype/channels"); return FRHIP_EINVAL; }
-    const int hp = (h - 1) / 2 + 1, wp = (w - 1) / 2 + 1;
-    const size_t total = (size_t)b * hp * wp * (c / epv);
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL(bn_relu_maxpool_fwd_kernel<bf16_t>, dim3(stem_grid(total)), dim3(256), 0, stream,
-                           (const bf16_t*)y, scale, shift, (bf16_t*)out, argmax, b, h, w, c);
-    else
-        hipLaunchKernelGGL(bn_relu_maxpool_fwd_kernel<float>, dim3(stem_grid(total)), dim3(256), 0, stream,
-                           (const float*)y, scale, shift, (float*)out, argmax, b, h, w, c);
-    return check_launch("frhip_bn_relu_maxpool_fwd");
+    return by_dtype(dtype, "frhip_bn_relu_maxpool_fwd", [&](auto t) {
+        typedef decltype(t) T;
+        constexpr int epv = 16 / (int)sizeof(T);
+        if (c % epv) { set_error("frhip_bn_relu_maxpool_fwd: bad dtype/channels"); return FRHIP_EINVAL; }
+        const int hp = (h - 1) / 2 + 1, wp = (w - 1) / 2 + 1;
+        const size_t total = (size_t)b * hp * wp * (c / epv);
+        hipLaunchKernelGGL(bn_relu_maxpool_fwd_kernel<T>, dim3(stem_grid(total)), dim3(256), 0, stream,
+                           (const T*)y, scale, shift, (T*)out, argmax, b, h, w, c);
+        return check_launch("frhip_bn_relu_maxpool_fwd");
+    });
 }
 
 extern "C" int frhip_maxpool_bwd(int dtype, const void* dpool, const uint8_t* argmax, void* da, int b, int h, int w,
                                  int c, hipStream_t stream) {
-    const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
-    if ((dtype != FRHIP_DT_BF16 && dtype != FRHIP_DT_F32) || (c % epv)) { set_error("frhip_maxpool_bwd: bad dtype/channels"); return FRHIP_EINVAL; }
-    const size_t total = (size_t)b * h * w * (c / epv);
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(stem_grid(total)), dim3(256), 0, stream,
-                           (const bf16_t*)dpool, argmax, (bf16_t*)da, b, h, w, c);
-    else
-        hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(stem_grid(total)), dim3(256), 0, stream,
-                           (const float*)dpool, argmax, (float*)da, b, h, w, c);
-    return check_launch("frhip_maxpool_bwd");
+    return by_dtype(dtype, "frhip_maxpool_bwd", [&](auto t) {
+        typedef decltype(t) T;
+        constexpr int epv = 16 / (int)sizeof(T);
+        if (c % epv) { set_error("frhip_maxpool_bwd: bad dtype/channels"); return FRHIP_EINVAL; }
+        const size_t total = (size_t)b * h * w * (c / epv);
+        hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3(stem_grid(total)), dim3(256), 0, stream,
+                           (const T*)dpool, argmax, (T*)da, b, h, w, c);
+        return check_launch("frhip_maxpool_bwd");
+    });
 }

@@ -264,36 +264,34 @@ extern "C" int frhip_stem_gram_blocks(int b, int h, int w) {
 }
 
 extern "C" int frhip_stem_gram(int dtype, const float* x, int b, int h, int w, float* partial, float* gram, hipStream_t stream) {
-    if (!sa_ok(dtype, b, h, w, "frhip_stem_gram")) return FRHIP_EINVAL;
-    const int blocks = frhip_stem_gram_blocks(b, h, w);
-    int lds = 3 * (SG_ROWS + 2) * (w + 2) * 4;
-    if (lds < 4 * 8 * SG_VALS * 4) lds = 4 * 8 * SG_VALS * 4;
-    if (dtype == FRHIP_DT_BF16) hipLaunchKernelGGL(stem_gram_kernel<bf16_t>, dim3(blocks), dim3(256), lds, stream, x, partial, b, h, w);
-    else hipLaunchKernelGGL(stem_gram_kernel<float>, dim3(blocks), dim3(256), lds, stream, x, partial, b, h, w);
-    int rc = check_launch("frhip_stem_gram");
-    if (rc) return rc;
-    float* blk = partial + (size_t)blocks * SG_OUT;            // 567 more floats of the caller's scratch
-    hipLaunchKernelGGL(stem_gram_fold_kernel, dim3(7), dim3(256), 0, stream, partial, blocks, blk);
-    hipLaunchKernelGGL(stem_gram_assemble_kernel, dim3(1), dim3(256), 0, stream, blk, gram);
-    return check_launch("frhip_stem_gram(reduce)");
+    return by_dtype(dtype, "frhip_stem_gram", [&](auto t) {
+        typedef decltype(t) T;
+        if (!sa_ok(dtype, b, h, w, "frhip_stem_gram")) return FRHIP_EINVAL;
+        const int blocks = frhip_stem_gram_blocks(b, h, w);
+        int lds = 3 * (SG_ROWS + 2) * (w + 2) * 4;
+        if (lds < 4 * 8 * SG_VALS * 4) lds = 4 * 8 * SG_VALS * 4;
+        hipLaunchKernelGGL(stem_gram_kernel<T>, dim3(blocks), dim3(256), lds, stream, x, partial, b, h, w);
+        int rc = check_launch("frhip_stem_gram");
+        if (rc) return rc;
+        float* blk = partial + (size_t)blocks * SG_OUT;            // 567 more floats of the caller's scratch
+        hipLaunchKernelGGL(stem_gram_fold_kernel, dim3(7), dim3(256), 0, stream, partial, blocks, blk);
+        hipLaunchKernelGGL(stem_gram_assemble_kernel, dim3(1), dim3(256), 0, stream, blk, gram);
+        return check_launch("frhip_stem_gram(reduce)");
+    });
 }
 
 extern "C" int frhip_stem_bwd_wgrad_gram(int dtype, const float* x, const void* wp, const void* dpool, const void* pooled,
                                          const uint8_t* argmax, const float* gram, const float* ca, const float* cb, const float* cc,
                                          int b, int h, int w, float* slabs, float* dw, hipStream_t stream) {
-    if (!sa_ok(dtype, b, h, w, "frhip_stem_bwd_wgrad_gram")) return FRHIP_EINVAL;
-    const int blocks = frhip_stem_blocks(b, h, w);
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL(stem_dgather_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, x, (const bf16_t*)dpool, (const bf16_t*)pooled,
+    return by_dtype(dtype, "frhip_stem_bwd_wgrad_gram", [&](auto t) {
+        typedef decltype(t) T;
+        if (!sa_ok(dtype, b, h, w, "frhip_stem_bwd_wgrad_gram")) return FRHIP_EINVAL;
+        const int blocks = frhip_stem_blocks(b, h, w);
+        hipLaunchKernelGGL(stem_dgather_kernel<T>, dim3(blocks), dim3(256), 0, stream, x, (const T*)dpool, (const T*)pooled,
                            argmax, slabs, b, h, w);
-    else
-        hipLaunchKernelGGL(stem_dgather_kernel<float>, dim3(blocks), dim3(256), 0, stream, x, (const float*)dpool, (const float*)pooled,
-                           argmax, slabs, b, h, w);
-    int rc = check_launch("frhip_stem_bwd_wgrad_gram(gather)");
-    if (rc) return rc;
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL(stem_dw_final_kernel<bf16_t>, dim3(64), dim3(1024), 0, stream, slabs, blocks, gram, (const bf16_t*)wp, ca, cb, cc, dw);
-    else
-        hipLaunchKernelGGL(stem_dw_final_kernel<float>, dim3(64), dim3(1024), 0, stream, slabs, blocks, gram, (const float*)wp, ca, cb, cc, dw);
-    return check_launch("frhip_stem_bwd_wgrad_gram(final)");
+        int rc = check_launch("frhip_stem_bwd_wgrad_gram(gather)");
+        if (rc) return rc;
+        hipLaunchKernelGGL(stem_dw_final_kernel<T>, dim3(64), dim3(1024), 0, stream, slabs, blocks, gram, (const T*)wp, ca, cb, cc, dw);
+        return check_launch("frhip_stem_bwd_wgrad_gram(final)");
+    });
 }

@@ -17,6 +17,7 @@
 // lane layout the MFMA wants -- lane (i = lane & 15, g = lane >> 4) holds k = run*4*EPL + g*EPL + e of pixel i --
 // A operand = packed weights [64][32]; D: lane holds channels t*16 + 4g + reg of pixel i.
 #include "common.h"
+#include "tr_frag.h"
 #include "frhip.h"
 
 namespace frhip {
@@ -84,42 +85,6 @@ struct StemConv {
 #pragma unroll
             for (int r = 0; r < RUNS; ++r) Mma<T>::run(wf[r][t], b[r], acc[t]);
         }
-    }
-};
-
-// [pixel][channel] LDS tiles read as K = pixel MFMA fragments (the layout rules of igemm_tn.hip: 16-byte chunks XOR-swizzled
-// per row so that the transposing read ds_read_b64_tr_b16 / the strided f32 reads are bank-conflict free)
-template <int RB> __device__ __forceinline__ int sf_swz(int row);
-template <> __device__ __forceinline__ int sf_swz<256>(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-template <> __device__ __forceinline__ int sf_swz<128>(int row) { return (((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 1; }
-
-template <typename T, int RB> struct SfFrag;
-template <int RB> struct SfFrag<bf16_t, RB> {
-    static constexpr int KROWS = 32;     // pixels per MFMA group
-    __device__ static __forceinline__ bf16x8_t load(const char* tile, int c0, int lane) {
-        const int g = lane >> 4, j = lane & 15, q = j >> 2, p = j & 3;
-        const int chunk = (c0 >> 3) + (p >> 1);
-        const int row_a = 8 * g + q, row_b = row_a + 4;
-        const char* pa = tile + row_a * RB + ((chunk ^ sf_swz<RB>(row_a)) << 4) + 8 * (p & 1);
-        const char* pb = tile + row_b * RB + ((chunk ^ sf_swz<RB>(row_b)) << 4) + 8 * (p & 1);
-        i16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4_t*)LDS_ADDR(pa));
-        i16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4_t*)LDS_ADDR(pb));
-        typedef __attribute__((ext_vector_type(8))) short i16x8_t;
-        return __builtin_bit_cast(bf16x8_t, (i16x8_t)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    }
-};
-template <int RB> struct SfFrag<float, RB> {
-    static constexpr int KROWS = 16;
-    __device__ static __forceinline__ f32x4_t load(const char* tile, int c0, int lane) {
-        const int g = lane >> 4, i = lane & 15;
-        const int col = c0 + i, chunk = col >> 2, within = (col & 3) * 4;
-        f32x4_t v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int row = 4 * e + g;
-            v[e] = *reinterpret_cast<const float*>(tile + row * RB + ((chunk ^ sf_swz<RB>(row)) << 4) + within);
-        }
-        return v;
     }
 };
 
@@ -291,7 +256,7 @@ __global__ __launch_bounds__(256, 2) void stem_bwd_kernel(const float* __restric
     constexpr int DROW = 64 * (int)sizeof(T) + 16;           // bytes per pooled pixel in the dpool tile (+16: bank spread)
     constexpr int AROW = 64 + 16;                            // bytes per pooled pixel in the arg-max tile
     constexpr int DY_RB = 64 * (int)sizeof(T), COL_RB = 128; // wgrad staging rows: 64 channels / 32 k-values (bf16: half used)
-    constexpr int KR = SfFrag<T, 128>::KROWS;                // pixels per weight-gradient MFMA group: 32 (bf16) / 16 (f32)
+    constexpr int KR = TnFrag<T, 128>::KROWS;                // pixels per weight-gradient MFMA group: 32 (bf16) / 16 (f32)
     constexpr int SUB = KR / 16;                             // 16-pixel conv iterations per weight-gradient group
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* s_dp = smem;                                        // [TH*TW][DROW]
@@ -421,7 +386,7 @@ __global__ __launch_bounds__(256, 2) void stem_bwd_kernel(const float* __restric
                     for (int t = 0; t < 4; ++t) {
                         constexpr int CPV = 16 / (int)sizeof(T);                   // channels per 16-byte chunk
                         const int ch0 = t * 16 + 4 * g;
-                        char* dst = my_dy + row * DY_RB + (((ch0 / CPV) ^ sf_swz<DY_RB>(row)) << 4) + (ch0 % CPV) * (int)sizeof(T);
+                        char* dst = my_dy + row * DY_RB + (((ch0 / CPV) ^ tn_swz<DY_RB>(row)) << 4) + (ch0 % CPV) * (int)sizeof(T);
                         if constexpr (sizeof(T) == 2) {
                             bf16x4_t q;
 #pragma unroll
@@ -435,7 +400,7 @@ __global__ __launch_bounds__(256, 2) void stem_bwd_kernel(const float* __restric
                     for (int rn = 0; rn < RUNS; ++rn) {
                         // k-values rn*4*EPL + g*EPL .. + EPL of this pixel = one 16-byte chunk
                         const int chunk = rn * 4 + g;
-                        *reinterpret_cast<typename StemConv<T>::Frag*>(my_col + row * COL_RB + ((chunk ^ sf_swz<COL_RB>(row)) << 4)) = b[rn];
+                        *reinterpret_cast<typename StemConv<T>::Frag*>(my_col + row * COL_RB + ((chunk ^ tn_swz<COL_RB>(row)) << 4)) = b[rn];
                     }
                 }
             }
@@ -443,9 +408,9 @@ __global__ __launch_bounds__(256, 2) void stem_bwd_kernel(const float* __restric
                 // dW[co][k] += sum over the KR staged pixels of dy[pix][co] * col[pix][k]  (K = pixel MFMA, fragments transposed-read)
                 typename StemConv<T>::Frag af[4], bf[2];
 #pragma unroll
-                for (int t = 0; t < 4; ++t) af[t] = SfFrag<T, DY_RB>::load(my_dy, t * 16, lane);
+                for (int t = 0; t < 4; ++t) af[t] = TnFrag<T, DY_RB>::load(my_dy, 0, t * 16, lane);
 #pragma unroll
-                for (int kt = 0; kt < 2; ++kt) bf[kt] = SfFrag<T, COL_RB>::load(my_col, kt * 16, lane);
+                for (int kt = 0; kt < 2; ++kt) bf[kt] = TnFrag<T, COL_RB>::load(my_col, 0, kt * 16, lane);
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -510,7 +475,7 @@ constexpr int SB_LDS_REDUCE = SB_OFF_MASK > SB_THREADS * 16 * 4 ? SB_OFF_MASK : 
 constexpr int SB_LDS_WGRAD = SB_OFF_COL + SB_WAVES * 32 * 128;
 
 // byte address of channel c of pixel row `row` in the [pixel][64 ch] bf16 tile (16-byte chunks swizzled per row)
-__device__ __forceinline__ int sb_addr(int row, int c) { return row * 128 + (((c >> 3) ^ sf_swz<128>(row)) << 4) + (c & 7) * 2; }
+__device__ __forceinline__ int sb_addr(int row, int c) { return row * 128 + (((c >> 3) ^ tn_swz<128>(row)) << 4) + (c & 7) * 2; }
 
 template <bool WGRAD>
 __global__ __launch_bounds__(SB_THREADS, 1) void stem_bwd2_kernel(const float* __restrict__ x, const bf16_t* __restrict__ wp,
@@ -658,13 +623,13 @@ __global__ __launch_bounds__(SB_THREADS, 1) void stem_bwd2_kernel(const float* _
                     typename StemConv<T>::Frag b[1];
                     sc.gather(br, bc, true, b);
                     const int row = sub * 16 + i;
-                    *reinterpret_cast<bf16x8_t*>(my_col + row * 128 + ((g ^ sf_swz<128>(row)) << 4)) = b[0];
+                    *reinterpret_cast<bf16x8_t*>(my_col + row * 128 + ((g ^ tn_swz<128>(row)) << 4)) = b[0];
                 }
                 bf16x8_t af[4], bf[2];
 #pragma unroll
-                for (int t = 0; t < 4; ++t) af[t] = SfFrag<T, 128>::load(s_tile + grp * 32 * 128, t * 16, lane);
+                for (int t = 0; t < 4; ++t) af[t] = TnFrag<T, 128>::load(s_tile + grp * 32 * 128, 0, t * 16, lane);
 #pragma unroll
-                for (int kt = 0; kt < 2; ++kt) bf[kt] = SfFrag<T, 128>::load(my_col, kt * 16, lane);
+                for (int kt = 0; kt < 2; ++kt) bf[kt] = TnFrag<T, 128>::load(my_col, 0, kt * 16, lane);
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -983,17 +948,16 @@ static bool sf_ok(int dtype, int b, int h, int w, const char* who) {
 
 extern "C" int frhip_stem_stats(int dtype, const float* x, const void* wp, int b, int h, int w, float* partial,
                                 hipStream_t stream) {
-    if (!sf_ok(dtype, b, h, w, "frhip_stem_stats")) return FRHIP_EINVAL;
-    const int blocks = frhip_stem_blocks(b, h, w);
-    const int es = dtype == FRHIP_DT_BF16 ? 2 : 4;
-    int lds = 3 * 10 * (w + 2) * es;
-    if (lds < 4 * 2 * 64 * 4) lds = 4 * 2 * 64 * 4;
-    if (lds > 64 * 1024) { set_error("frhip_stem_stats: image too wide (%d)", w); return FRHIP_EINVAL; }
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL(stem_stats_kernel<bf16_t>, dim3(blocks), dim3(256), lds, stream, x, (const bf16_t*)wp, partial, b, h, w);
-    else
-        hipLaunchKernelGGL(stem_stats_kernel<float>, dim3(blocks), dim3(256), lds, stream, x, (const float*)wp, partial, b, h, w);
-    return check_launch("frhip_stem_stats");
+    return by_dtype(dtype, "frhip_stem_stats", [&](auto t) {
+        typedef decltype(t) T;
+        if (!sf_ok(dtype, b, h, w, "frhip_stem_stats")) return FRHIP_EINVAL;
+        const int blocks = frhip_stem_blocks(b, h, w);
+        int lds = 3 * 10 * (w + 2) * (int)sizeof(T);
+        if (lds < 4 * 2 * 64 * 4) lds = 4 * 2 * 64 * 4;
+        if (lds > 64 * 1024) { set_error("frhip_stem_stats: image too wide (%d)", w); return FRHIP_EINVAL; }
+        hipLaunchKernelGGL(stem_stats_kernel<T>, dim3(blocks), dim3(256), lds, stream, x, (const T*)wp, partial, b, h, w);
+        return check_launch("frhip_stem_stats");
+    });
 }
 
 template <typename T>
@@ -1008,9 +972,10 @@ static int sf_fwd(const float* x, const void* wp, const float* scale, const floa
 
 extern "C" int frhip_stem_fwd(int dtype, const float* x, const void* wp, const float* scale, const float* shift,
                               void* pooled, uint8_t* argmax, int b, int h, int w, hipStream_t stream) {
-    if (!sf_ok(dtype, b, h, w, "frhip_stem_fwd")) return FRHIP_EINVAL;
-    return dtype == FRHIP_DT_BF16 ? sf_fwd<bf16_t>(x, wp, scale, shift, pooled, argmax, b, h, w, stream)
-                                  : sf_fwd<float>(x, wp, scale, shift, pooled, argmax, b, h, w, stream);
+    return by_dtype(dtype, "frhip_stem_fwd", [&](auto t) {
+        if (!sf_ok(dtype, b, h, w, "frhip_stem_fwd")) return FRHIP_EINVAL;
+        return sf_fwd<decltype(t)>(x, wp, scale, shift, pooled, argmax, b, h, w, stream);
+    });
 }
 
 template <typename T, bool WGRAD>
@@ -1048,26 +1013,27 @@ static int g_stem_scatter = 1;       // test hook: 0 = gather-form backward for 
 extern "C" int frhip_stem_bwd_reduce(int dtype, const float* x, const void* wp, const void* dpool, const uint8_t* argmax,
                                      const float* mean, const float* invstd, const float* scale, const float* shift,
                                      int b, int h, int w, float* partial, hipStream_t stream) {
-    if (!sf_ok(dtype, b, h, w, "frhip_stem_bwd_reduce")) return FRHIP_EINVAL;
-    if (dtype == FRHIP_DT_BF16 && g_stem_scatter)
-        return sf_bwd2<false>(x, wp, dpool, argmax, mean, invstd, nullptr, scale, shift, partial, b, h, w, stream, "frhip_stem_bwd_reduce");
-    return dtype == FRHIP_DT_BF16
-        ? sf_bwd<bf16_t, false>(x, wp, dpool, argmax, mean, invstd, nullptr, scale, shift, partial, b, h, w, stream, "frhip_stem_bwd_reduce")
-        : sf_bwd<float, false>(x, wp, dpool, argmax, mean, invstd, nullptr, scale, shift, partial, b, h, w, stream, "frhip_stem_bwd_reduce");
+    return by_dtype(dtype, "frhip_stem_bwd_reduce", [&](auto t) {
+        if (!sf_ok(dtype, b, h, w, "frhip_stem_bwd_reduce")) return FRHIP_EINVAL;
+        if (dtype == FRHIP_DT_BF16 && g_stem_scatter)
+            return sf_bwd2<false>(x, wp, dpool, argmax, mean, invstd, nullptr, scale, shift, partial, b, h, w, stream, "frhip_stem_bwd_reduce");
+        return sf_bwd<decltype(t), false>(x, wp, dpool, argmax, mean, invstd, nullptr, scale, shift, partial, b, h, w, stream,
+                                          "frhip_stem_bwd_reduce");
+    });
 }
 
 extern "C" int frhip_stem_bwd_wgrad(int dtype, const float* x, const void* wp, const void* dpool, const uint8_t* argmax,
                                     const float* ca, const float* cb, const float* cc, const float* scale, const float* shift,
                                     int b, int h, int w, float* slabs, float* dw, hipStream_t stream) {
-    if (!sf_ok(dtype, b, h, w, "frhip_stem_bwd_wgrad")) return FRHIP_EINVAL;
-    int rc = (dtype == FRHIP_DT_BF16 && g_stem_scatter)
-        ? sf_bwd2<true>(x, wp, dpool, argmax, ca, cb, cc, scale, shift, slabs, b, h, w, stream, "frhip_stem_bwd_wgrad")
-        : dtype == FRHIP_DT_BF16
-        ? sf_bwd<bf16_t, true>(x, wp, dpool, argmax, ca, cb, cc, scale, shift, slabs, b, h, w, stream, "frhip_stem_bwd_wgrad")
-        : sf_bwd<float, true>(x, wp, dpool, argmax, ca, cb, cc, scale, shift, slabs, b, h, w, stream, "frhip_stem_bwd_wgrad");
-    if (rc) return rc;
-    hipLaunchKernelGGL(stem_dw_reduce_kernel, dim3(64 * 27), dim3(256), 0, stream, slabs, frhip_stem_blocks(b, h, w), dw);
-    return check_launch("frhip_stem_bwd_wgrad(reduce)");
+    return by_dtype(dtype, "frhip_stem_bwd_wgrad", [&](auto t) {
+        if (!sf_ok(dtype, b, h, w, "frhip_stem_bwd_wgrad")) return FRHIP_EINVAL;
+        int rc = (dtype == FRHIP_DT_BF16 && g_stem_scatter)
+            ? sf_bwd2<true>(x, wp, dpool, argmax, ca, cb, cc, scale, shift, slabs, b, h, w, stream, "frhip_stem_bwd_wgrad")
+            : sf_bwd<decltype(t), true>(x, wp, dpool, argmax, ca, cb, cc, scale, shift, slabs, b, h, w, stream, "frhip_stem_bwd_wgrad");
+        if (rc) return rc;
+        hipLaunchKernelGGL(stem_dw_reduce_kernel, dim3(64 * 27), dim3(256), 0, stream, slabs, frhip_stem_blocks(b, h, w), dw);
+        return check_launch("frhip_stem_bwd_wgrad(reduce)");
+    });
 }
 
 extern "C" int frhip_set_stem_scatter(int enabled) { const int old = g_stem_scatter; g_stem_scatter = enabled; return old; }
@@ -1086,30 +1052,29 @@ static int sf_dx(const float* x, const void* wp, const void* dpool, const uint8_
 
 extern "C" int frhip_stem_dx(int dtype, const float* x, const void* wp, const void* dpool, const uint8_t* argmax, const void* pooled,
                              const float* ca, const float* cb, const float* cc, int b, int h, int w, float* dx, hipStream_t stream) {
-    if (!sf_ok(dtype, b, h, w, "frhip_stem_dx")) return FRHIP_EINVAL;
-    const bool recomp = cb != nullptr || cc != nullptr;
-    if (!wp || !dpool || !argmax || !pooled || !ca || !dx || (recomp && (!cb || !cc || !x))) {
-        set_error("frhip_stem_dx: missing operand (cb and cc are both given, with x, or both NULL)");
-        return FRHIP_EINVAL;
-    }
-    if (dtype == FRHIP_DT_BF16)
-        return recomp ? sf_dx<bf16_t, true>(x, wp, dpool, argmax, pooled, ca, cb, cc, dx, b, h, w, stream)
-                      : sf_dx<bf16_t, false>(x, wp, dpool, argmax, pooled, ca, cb, cc, dx, b, h, w, stream);
-    return recomp ? sf_dx<float, true>(x, wp, dpool, argmax, pooled, ca, cb, cc, dx, b, h, w, stream)
-                  : sf_dx<float, false>(x, wp, dpool, argmax, pooled, ca, cb, cc, dx, b, h, w, stream);
+    return by_dtype(dtype, "frhip_stem_dx", [&](auto t) {
+        typedef decltype(t) T;
+        if (!sf_ok(dtype, b, h, w, "frhip_stem_dx")) return FRHIP_EINVAL;
+        const bool recomp = cb != nullptr || cc != nullptr;
+        if (!wp || !dpool || !argmax || !pooled || !ca || !dx || (recomp && (!cb || !cc || !x))) {
+            set_error("frhip_stem_dx: missing operand (cb and cc are both given, with x, or both NULL)");
+            return FRHIP_EINVAL;
+        }
+        return recomp ? sf_dx<T, true>(x, wp, dpool, argmax, pooled, ca, cb, cc, dx, b, h, w, stream)
+                      : sf_dx<T, false>(x, wp, dpool, argmax, pooled, ca, cb, cc, dx, b, h, w, stream);
+    });
 }
 
 extern "C" int frhip_stem_dx_s2(int dtype, const void* dy0, const void* wp, int kp, int b, int h, int w, float* dx, hipStream_t stream) {
-    if (!sf_ok(dtype, b, h, w, "frhip_stem_dx_s2")) return FRHIP_EINVAL;
-    if (!dy0 || !wp || !dx || kp < 27) { set_error("frhip_stem_dx_s2: bad arguments (kp=%d)", kp); return FRHIP_EINVAL; }
-    const long long total = (long long)b * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1);     // 2 x 2 quads
-    long long blocks = (total + 255) / 256;
-    if (blocks > 65536) blocks = 65536;                    // grid-stride beyond
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL(stem_dx_s2_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, stream, (const bf16_t*)dy0, (const bf16_t*)wp,
+    return by_dtype(dtype, "frhip_stem_dx_s2", [&](auto t) {
+        typedef decltype(t) T;
+        if (!sf_ok(dtype, b, h, w, "frhip_stem_dx_s2")) return FRHIP_EINVAL;
+        if (!dy0 || !wp || !dx || kp < 27) { set_error("frhip_stem_dx_s2: bad arguments (kp=%d)", kp); return FRHIP_EINVAL; }
+        const long long total = (long long)b * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1);     // 2 x 2 quads
+        long long blocks = (total + 255) / 256;
+        if (blocks > 65536) blocks = 65536;                    // grid-stride beyond
+        hipLaunchKernelGGL(stem_dx_s2_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, stream, (const T*)dy0, (const T*)wp,
                            kp, dx, b, h, w);
-    else
-        hipLaunchKernelGGL(stem_dx_s2_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)dy0, (const float*)wp,
-                           kp, dx, b, h, w);
-    return check_launch("frhip_stem_dx_s2");
+        return check_launch("frhip_stem_dx_s2");
+    });
 }

@@ -358,69 +358,74 @@ extern "C" int frhip_set_winattn_mfma(int enabled) {
 
 extern "C" int frhip_winattn_fwd(int dtype, const void* qkv, const float* bias, const float* scale, void* out, int b, int h,
                                  int w, int c, int heads, int ws, int shift, hipStream_t stream) {
-    if (!wa_shape_ok(dtype, b, h, w, c, heads, ws, shift, "frhip_winattn_fwd")) return FRHIP_EINVAL;
-    const int nwin = b * (h / ws) * (w / ws);
-    WaGeom g; g.H = h; g.W = w; g.ws = ws; g.shift = shift; g.n = ws * ws;
-    if (dtype == FRHIP_DT_BF16 && g_wa_mfma) return winattn_mfma_fwd(qkv, bias, scale, out, nwin, g, c, heads, stream);
-    const int blocks = (nwin * heads + 3) / 4, lds = 4 * wa_per_wave(1) * 4;
-    const void* fn = dtype == FRHIP_DT_BF16 ? reinterpret_cast<const void*>(winattn_fwd_kernel<bf16_t>) : reinterpret_cast<const void*>(winattn_fwd_kernel<float>);
-    if (set_dynamic_lds(fn, lds, "frhip_winattn_fwd")) return FRHIP_ELAUNCH;
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL(winattn_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), lds, stream, (const bf16_t*)qkv, bias, scale, (bf16_t*)out, nwin, g, c, heads);
-    else
-        hipLaunchKernelGGL(winattn_fwd_kernel<float>, dim3(blocks), dim3(256), lds, stream, (const float*)qkv, bias, scale, (float*)out, nwin, g, c, heads);
-    return check_launch("frhip_winattn_fwd");
+    return by_dtype(dtype, "frhip_winattn_fwd", [&](auto t) {
+        typedef decltype(t) T;
+        if (!wa_shape_ok(dtype, b, h, w, c, heads, ws, shift, "frhip_winattn_fwd")) return FRHIP_EINVAL;
+        const int nwin = b * (h / ws) * (w / ws);
+        WaGeom g; g.H = h; g.W = w; g.ws = ws; g.shift = shift; g.n = ws * ws;
+        if (dtype == FRHIP_DT_BF16 && g_wa_mfma) return winattn_mfma_fwd(qkv, bias, scale, out, nwin, g, c, heads, stream);
+        const int blocks = (nwin * heads + 3) / 4, lds = 4 * wa_per_wave(1) * 4;
+        if (set_dynamic_lds(reinterpret_cast<const void*>(winattn_fwd_kernel<T>), lds, "frhip_winattn_fwd")) return FRHIP_ELAUNCH;
+        hipLaunchKernelGGL(winattn_fwd_kernel<T>, dim3(blocks), dim3(256), lds, stream, (const T*)qkv, bias, scale, (T*)out, nwin, g, c, heads);
+        return check_launch("frhip_winattn_fwd");
+    });
 }
 
 extern "C" int frhip_winattn_bwd(int dtype, const void* qkv, const void* dout, const float* bias, const float* scale,
                                  void* dqkv, float* dbias, float* dscale, int b, int h, int w, int c, int heads,
                                  int ws, int shift, float* workspace, size_t workspace_bytes, hipStream_t stream) {
-    if (!wa_shape_ok(dtype, b, h, w, c, heads, ws, shift, "frhip_winattn_bwd")) return FRHIP_EINVAL;
-    const int nwin = b * (h / ws) * (w / ws);
-    WaGeom g; g.H = h; g.W = w; g.ws = ws; g.shift = shift; g.n = ws * ws;
-    const WaColsum none = {{nullptr, nullptr, nullptr}};
-    if (dtype == FRHIP_DT_BF16 && g_wa_mfma)
-        return winattn_mfma_bwd(qkv, dout, bias, scale, dqkv, dbias, dscale, none, nwin, g, c, heads, workspace, workspace_bytes, stream);
-    int chunks = (1024 + heads - 1) / heads;                 // ~1024 workgroups
-    int wpb = (nwin + chunks - 1) / chunks; if (wpb < 4) wpb = 4;
-    chunks = (nwin + wpb - 1) / wpb;
-    if (!workspace || (size_t)heads * chunks * WA_PART * sizeof(float) > workspace_bytes) {
-        set_error("frhip_winattn_bwd: the workspace must hold %d partial-sum slots of %d floats", heads * chunks, WA_PART);
-        return FRHIP_EINVAL;
-    }
-    const int lds = 4 * wa_per_wave(2) * 4;
-    const void* fn = dtype == FRHIP_DT_BF16 ? reinterpret_cast<const void*>(winattn_bwd_kernel<bf16_t>) : reinterpret_cast<const void*>(winattn_bwd_kernel<float>);
-    if (set_dynamic_lds(fn, lds, "frhip_winattn_bwd")) return FRHIP_ELAUNCH;
-    if (dtype == FRHIP_DT_BF16)
-        hipLaunchKernelGGL(winattn_bwd_kernel<bf16_t>, dim3(heads, chunks), dim3(256), lds, stream, (const bf16_t*)qkv, (const bf16_t*)dout, bias, scale, (bf16_t*)dqkv, workspace, nwin, g, c, heads, wpb);
-    else
-        hipLaunchKernelGGL(winattn_bwd_kernel<float>, dim3(heads, chunks), dim3(256), lds, stream, (const float*)qkv, (const float*)dout, bias, scale, (float*)dqkv, workspace, nwin, g, c, heads, wpb);
-    const int rc = check_launch("frhip_winattn_bwd");
-    return rc ? rc : wa_reduce_parts(workspace, chunks, heads, g.n, dbias, dscale, none, stream);
+    return by_dtype(dtype, "frhip_winattn_bwd", [&](auto t) {
+        typedef decltype(t) T;
+        if (!wa_shape_ok(dtype, b, h, w, c, heads, ws, shift, "frhip_winattn_bwd")) return FRHIP_EINVAL;
+        const int nwin = b * (h / ws) * (w / ws);
+        WaGeom g; g.H = h; g.W = w; g.ws = ws; g.shift = shift; g.n = ws * ws;
+        const WaColsum none = {{nullptr, nullptr, nullptr}};
+        if (dtype == FRHIP_DT_BF16 && g_wa_mfma)
+            return winattn_mfma_bwd(qkv, dout, bias, scale, dqkv, dbias, dscale, none, nwin, g, c, heads, workspace, workspace_bytes, stream);
+        int chunks = (1024 + heads - 1) / heads;                 // ~1024 workgroups
+        int wpb = (nwin + chunks - 1) / chunks; if (wpb < 4) wpb = 4;
+        chunks = (nwin + wpb - 1) / wpb;
+        if (!workspace || (size_t)heads * chunks * WA_PART * sizeof(float) > workspace_bytes) {
+            set_error("frhip_winattn_bwd: the workspace must hold %d partial-sum slots of %d floats", heads * chunks, WA_PART);
+            return FRHIP_EINVAL;
+        }
+        const int lds = 4 * wa_per_wave(2) * 4;
+        if (set_dynamic_lds(reinterpret_cast<const void*>(winattn_bwd_kernel<T>), lds, "frhip_winattn_bwd")) return FRHIP_ELAUNCH;
+        hipLaunchKernelGGL(winattn_bwd_kernel<T>, dim3(heads, chunks), dim3(256), lds, stream, (const T*)qkv, (const T*)dout, bias, scale,
+                           (T*)dqkv, workspace, nwin, g, c, heads, wpb);
+        const int rc = check_launch("frhip_winattn_bwd");
+        return rc ? rc : wa_reduce_parts(workspace, chunks, heads, g.n, dbias, dscale, none, stream);
+    });
 }
 
 extern "C" int frhip_bias_gelu_fwd(int dtype, void* y, const float* bias, void* act_out, int rows, int c, hipStream_t stream) {
-    const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
-    if ((dtype != FRHIP_DT_BF16 && dtype != FRHIP_DT_F32) || (c % epv)) { set_error("frhip_bias_gelu_fwd: bad dtype/channels"); return FRHIP_EINVAL; }
-    const size_t nvec = (size_t)rows * c / epv;
-    if (dtype == FRHIP_DT_BF16) hipLaunchKernelGGL(bias_gelu_fwd_kernel<bf16_t>, dim3(ew_blocks(nvec)), dim3(256), 0, stream, (bf16_t*)y, bias, (bf16_t*)act_out, nvec, c);
-    else hipLaunchKernelGGL(bias_gelu_fwd_kernel<float>, dim3(ew_blocks(nvec)), dim3(256), 0, stream, (float*)y, bias, (float*)act_out, nvec, c);
-    return check_launch("frhip_bias_gelu_fwd");
+    return by_dtype(dtype, "frhip_bias_gelu_fwd", [&](auto t) {
+        typedef decltype(t) T;
+        constexpr int epv = 16 / (int)sizeof(T);
+        if (c % epv) { set_error("frhip_bias_gelu_fwd: bad dtype/channels"); return FRHIP_EINVAL; }
+        const size_t nvec = (size_t)rows * c / epv;
+        hipLaunchKernelGGL(bias_gelu_fwd_kernel<T>, dim3(ew_blocks(nvec)), dim3(256), 0, stream, (T*)y, bias, (T*)act_out, nvec, c);
+        return check_launch("frhip_bias_gelu_fwd");
+    });
 }
 
 extern "C" int frhip_gelu_bwd(int dtype, const void* da, const void* h, void* dh, size_t n, hipStream_t stream) {
-    const int epv = dtype == FRHIP_DT_BF16 ? 8 : 4;
-    if ((dtype != FRHIP_DT_BF16 && dtype != FRHIP_DT_F32) || (n % epv)) { set_error("frhip_gelu_bwd: bad dtype/size"); return FRHIP_EINVAL; }
-    const size_t nvec = n / epv;
-    if (dtype == FRHIP_DT_BF16) hipLaunchKernelGGL(gelu_bwd_kernel<bf16_t>, dim3(ew_blocks(nvec)), dim3(256), 0, stream, (const bf16_t*)da, (const bf16_t*)h, (bf16_t*)dh, nvec);
-    else hipLaunchKernelGGL(gelu_bwd_kernel<float>, dim3(ew_blocks(nvec)), dim3(256), 0, stream, (const float*)da, (const float*)h, (float*)dh, nvec);
-    return check_launch("frhip_gelu_bwd");
+    return by_dtype(dtype, "frhip_gelu_bwd", [&](auto t) {
+        typedef decltype(t) T;
+        constexpr int epv = 16 / (int)sizeof(T);
+        if (n % epv) { set_error("frhip_gelu_bwd: bad dtype/size"); return FRHIP_EINVAL; }
+        const size_t nvec = n / epv;
+        hipLaunchKernelGGL(gelu_bwd_kernel<T>, dim3(ew_blocks(nvec)), dim3(256), 0, stream, (const T*)da, (const T*)h, (T*)dh, nvec);
+        return check_launch("frhip_gelu_bwd");
+    });
 }
 
+// The two column-sum calls serve bf16 only; fp32 is refused below, any other dtype by the dispatch
 extern "C" int frhip_winattn_bwd_colsum(int dtype, const void* qkv, const void* dout, const float* bias, const float* scale,
                                         void* dqkv, float* dbias, float* dscale, float* dqkv_colsum, int b, int h, int w,
                                         int c, int heads, int ws, int shift, float* workspace, size_t workspace_bytes,
                                         hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_winattn_bwd_colsum", [](auto) { return FRHIP_OK; })) return rc;
     if (!wa_shape_ok(dtype, b, h, w, c, heads, ws, shift, "frhip_winattn_bwd_colsum")) return FRHIP_EINVAL;
     if (dtype != FRHIP_DT_BF16 || !g_wa_mfma) {
         set_error("frhip_winattn_bwd_colsum: only the bf16 MFMA kernels produce the column sums (frhip_set_winattn_mfma)");
@@ -436,6 +441,7 @@ extern "C" int frhip_winattn_bwd_qvbias(int dtype, const void* qkv, const void* 
                                         void* dqkv, float* dbias, float* dscale, float* dq_bias, float* dv_bias, int b, int h,
                                         int w, int c, int heads, int ws, int shift, float* workspace, size_t workspace_bytes,
                                         hipStream_t stream) {
+    if (const int rc = by_dtype(dtype, "frhip_winattn_bwd_qvbias", [](auto) { return FRHIP_OK; })) return rc;
     if (!wa_shape_ok(dtype, b, h, w, c, heads, ws, shift, "frhip_winattn_bwd_qvbias")) return FRHIP_EINVAL;
     if (dtype != FRHIP_DT_BF16 || !g_wa_mfma) {
         set_error("frhip_winattn_bwd_qvbias: only the bf16 MFMA kernels produce the column sums (frhip_set_winattn_mfma)");

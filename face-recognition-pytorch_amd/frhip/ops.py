@@ -321,13 +321,19 @@ def _bwd_finalize(part, scratch, c, count, gamma, st, dgamma, dbeta, coef):
              _p(coef[0]), _p(coef[1]), _p(coef[2]), _s()), "frhip_bn_bwd_finalize_eval" if st.eval else "frhip_bn_bwd_finalize")
 
 
+def _bn_state(c, device, count, affine_only=False):
+    """BNState whose vectors are rows of one fresh fp32 buffer; affine_only: scale and shift alone (mean = invstd = None)"""
+    st = BNState()
+    buf = torch.empty((2 if affine_only else 4, c), dtype=torch.float32, device=device)
+    st.mean, st.invstd, st.scale, st.shift = (None, None, buf[0], buf[1]) if affine_only else (buf[0], buf[1], buf[2], buf[3])
+    st.count = count
+    return st
+
+
 def bn_standin_state(gamma, beta, k, count):
     """BNState(mean = beta, invstd = gamma / (gamma^2 + (k beta)^2 + 1e-20), scale = 1, shift = 0): frhip_bn_standin_state, one launch"""
     c = gamma.numel()
-    st = BNState()
-    buf = torch.empty((4, c), dtype=torch.float32, device=gamma.device)
-    st.mean, st.invstd, st.scale, st.shift = buf[0], buf[1], buf[2], buf[3]
-    st.count = count
+    st = _bn_state(c, gamma.device, count)
     check(lib().frhip_bn_standin_state(c, _p(gamma), _p(beta), float(k), _p(st.mean), _p(st.invstd), _p(st.scale), _p(st.shift), _s()),
           "frhip_bn_standin_state")
     return st
@@ -336,10 +342,7 @@ def bn_standin_state(gamma, beta, k, count):
 def bn_finalize(part, count, gamma, beta, running_mean, running_var, momentum=0.1, eps=1e-5, scratch=None):
     c = gamma.numel()
     dev = gamma.device
-    st = BNState()
-    buf = torch.empty((4, c), dtype=torch.float32, device=dev)
-    st.mean, st.invstd, st.scale, st.shift = buf[0], buf[1], buf[2], buf[3]
-    st.count = float(count)
+    st = _bn_state(c, dev, float(count))
     if scratch is None:
         scratch = torch.empty((64 * 2 * c,), dtype=torch.float32, device=dev)
     check(lib().frhip_bn_finalize(_p(part), part.shape[0], _p(scratch), c, float(count), _p(gamma), _p(beta),
@@ -350,11 +353,7 @@ def bn_finalize(part, count, gamma, beta, running_mean, running_var, momentum=0.
 
 def bn_eval_affine(gamma, beta, running_mean, running_var, eps=1e-5):
     c = gamma.numel()
-    st = BNState()
-    buf = torch.empty((2, c), dtype=torch.float32, device=gamma.device)
-    st.scale, st.shift = buf[0], buf[1]
-    st.mean = st.invstd = None
-    st.count = 0.0
+    st = _bn_state(c, gamma.device, 0.0, affine_only=True)
     check(lib().frhip_bn_eval_affine(c, _p(gamma), _p(beta), _p(running_mean), _p(running_var), eps, _p(st.scale),
                                      _p(st.shift), _s()), "frhip_bn_eval_affine")
     return st
@@ -364,10 +363,7 @@ def bn_eval_state(gamma, beta, running_mean, running_var, eps=1e-5):
     """eval-mode BatchNorm state of a pass that is differentiated: bn_eval_affine's scale / shift plus mean = running_mean and
     invstd = rsqrt(running_var + eps) (frhip_bn_eval_state, one launch)"""
     c = gamma.numel()
-    st = BNState()
-    buf = torch.empty((4, c), dtype=torch.float32, device=gamma.device)
-    st.mean, st.invstd, st.scale, st.shift = buf[0], buf[1], buf[2], buf[3]
-    st.count = 0.0
+    st = _bn_state(c, gamma.device, 0.0)
     st.eval = True
     check(lib().frhip_bn_eval_state(c, _p(gamma), _p(beta), _p(running_mean), _p(running_var), eps, _p(st.mean), _p(st.invstd),
                                     _p(st.scale), _p(st.shift), _s()), "frhip_bn_eval_state")
@@ -400,35 +396,31 @@ def bn_backward(dout, y, st, gamma, dgamma, dbeta, relu_mask=False, out=None, sc
     c = y.shape[-1]
     rows = y.numel() // c
     dev = y.device
-    if rowscale is not None:
+    rs = rowscale is not None
+    if rs:
         assert not relu_mask and rowscale.dtype == torch.float32 and rows == rowscale.numel() * rows_per
-        if part is None:           # else: the kernel that produced dout already took the sums (conv_dgrad(bnred=(..., rowscale, ...)))
-            nb = _colreduce_blocks(rows, c, dt_of(y))
-            part = torch.empty((nb, 2, c), dtype=torch.float32, device=dev)
-            check(lib().frhip_bn_bwd_reduce_rs(dt_of(y), _p(dout), _p(y), _p(st.mean), _p(st.invstd), _p(rowscale), rows_per, rows, c,
-                                               _p(part), _s()), "frhip_bn_bwd_reduce_rs")
-        coef = torch.empty((3, c), dtype=torch.float32, device=dev)
-        if scratch is None:
-            scratch = torch.empty((64 * 2 * c,), dtype=torch.float32, device=dev)
-        _bwd_finalize(part, scratch, c, rows, gamma, st, dgamma, dbeta, coef)
-        dy = torch.empty_like(y) if out is None else out
-        check(lib().frhip_bn_bwd_apply_rs(dt_of(y), _p(dout), _p(y), _p(coef[0]), _p(coef[1]), _p(coef[2]), _p(rowscale), rows_per,
-                                          _p(dy), rows, c, _s()), "frhip_bn_bwd_apply_rs")
-        return dy
     ms = _p(st.scale) if relu_mask else None
     mb = _p(st.shift) if relu_mask else None
-    if part is None:
+    if part is None:               # else: the kernel that produced dout already took the sums (conv_dgrad(bnred=...))
         nb = _colreduce_blocks(rows, c, dt_of(y))
         part = torch.empty((nb, 2, c), dtype=torch.float32, device=dev)
-        check(lib().frhip_bn_bwd_reduce(dt_of(y), _p(dout), _p(y), _p(st.mean), _p(st.invstd), ms, mb, rows, c, _p(part), _s()),
-              "frhip_bn_bwd_reduce")
+        if rs:
+            check(lib().frhip_bn_bwd_reduce_rs(dt_of(y), _p(dout), _p(y), _p(st.mean), _p(st.invstd), _p(rowscale), rows_per, rows, c,
+                                               _p(part), _s()), "frhip_bn_bwd_reduce_rs")
+        else:
+            check(lib().frhip_bn_bwd_reduce(dt_of(y), _p(dout), _p(y), _p(st.mean), _p(st.invstd), ms, mb, rows, c, _p(part), _s()),
+                  "frhip_bn_bwd_reduce")
     coef = torch.empty((3, c), dtype=torch.float32, device=dev)
     if scratch is None:
         scratch = torch.empty((64 * 2 * c,), dtype=torch.float32, device=dev)
     _bwd_finalize(part, scratch, c, rows, gamma, st, dgamma, dbeta, coef)
     dy = torch.empty_like(y) if out is None else out
-    check(lib().frhip_bn_bwd_apply(dt_of(y), _p(dout), _p(y), _p(coef[0]), _p(coef[1]), _p(coef[2]), ms, mb, _p(dy),
-                                   rows, c, _s()), "frhip_bn_bwd_apply")
+    if rs:
+        check(lib().frhip_bn_bwd_apply_rs(dt_of(y), _p(dout), _p(y), _p(coef[0]), _p(coef[1]), _p(coef[2]), _p(rowscale), rows_per,
+                                          _p(dy), rows, c, _s()), "frhip_bn_bwd_apply_rs")
+    else:
+        check(lib().frhip_bn_bwd_apply(dt_of(y), _p(dout), _p(y), _p(coef[0]), _p(coef[1]), _p(coef[2]), ms, mb, _p(dy),
+                                       rows, c, _s()), "frhip_bn_bwd_apply")
     return dy
 
 

@@ -38,3 +38,20 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_abi, "LIB_PATH", os.path.join(tmp_path, "nope.so"))
     with pytest.raises(_abi.FrhipError):
         _abi.lib()
+
+
+def test_unknown_dtype_is_refused_first_in_one_wording():
+    """Every prototype of frhip.h whose first parameter is `int dtype` and whose last is the stream, called with dtype 2 and zero / NULL
+    for the rest: it must say exactly "<name>: bad dtype 2" and return FRHIP_EINVAL before it reads another argument (a NULL dereference
+    or a division by a zero size would end the process, not the test)"""
+    from frhip import _abi
+    lib = _abi.lib()
+    protos = _abi.parse_header()
+    names = [name for _, name, params in _abi.prototypes()
+             if params and params[0] == "int dtype" and params[-1] == "frhip_stream_t stream"]
+    assert len(names) >= 60, names
+    for name in names:
+        args = [2] + [None if t is ctypes.c_void_p else t(0) for t in protos[name][1][1:]]
+        rc = getattr(lib, name)(*args)
+        assert rc == -1, (name, rc)
+        assert lib.frhip_last_error() == name.encode() + b": bad dtype 2", (name, lib.frhip_last_error())

@@ -77,6 +77,7 @@ def test_fp8_conv_matches_dequantised_reference(shape):
     x = torch.relu(recipe.normal(9710 + c, (n, h, w, c))).cuda().bfloat16()
     wt = recipe.normal(9720 + k, (k, r, r, c), 0.05).cuda()
     x8 = ops.quant_fp8(x)
+    assert torch.equal(ops.quant_fp8(x.float()), x8)     # the fp32 instantiation: the same values, the same bytes
     w8, ws = ops.quant_fp8_weights(wt)
     from frhip._abi import lib
     old = lib().frhip_set_fp8_halo(0)                    # generic NT kernel (block-scaled MFMA) ...

@@ -599,6 +599,11 @@ def test_packs_roundtrip():
     dst = torch.zeros((12, 64)).cuda()
     ops.scatter_rows(got.cuda(), idx.cuda(), dst)
     assert torch.equal(dst.cpu()[idx], src[idx])
+    for rows, c in ((3, 64), (7, 512)):                  # the two casts, each element type: exact against torch's rounding
+        x = rnd(33, (rows, c)).cuda()
+        for dt in DTYPES:
+            low = ops.cast_from_f32(x, dt)
+            assert low.dtype == dt and torch.equal(low, x.to(dt)) and torch.equal(ops.cast_to_f32(low), x.to(dt).float())
 
 
 @pytest.mark.parametrize("shape", [(8, 56, 56, 64, 64), (8, 28, 28, 128, 128), (16, 14, 14, 256, 256), (3, 14, 14, 256, 128),
