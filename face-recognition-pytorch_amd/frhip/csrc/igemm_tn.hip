@@ -12,6 +12,7 @@
 #include "common.h"
 #include "tr_frag.h"
 #include "frhip.h"
+#include "tn_plan.h"
 
 namespace frhip {
 
@@ -958,215 +959,103 @@ static int tn_launch(const TnGeom& g, const void* p, const void* q, float* out, 
     return check_launch("igemm_tn");
 }
 
-// K splits that added their partial tiles into `out` with fp32 atomics would sum them in whatever order they land, and the
-// weight gradient would change from run to run.  So a launch uses no more K splits than the workspace has slabs for (one split
-// -- each element added once -- where the slab path is closed).
-static int tn_slab_splits(int splits, size_t out_elems, const float* ws, size_t ws_bytes) {
-    if (splits <= 1) return splits;
-    if (!ws || (out_elems % 4)) return 1;
-    const size_t fit = ws_bytes / (out_elems * sizeof(float));
-    return fit < 1 ? 1 : ((size_t)splits > fit ? (int)fit : splits);
+// ---- host side: tn_plan.h decides (kernel, K split, slabs, reduce tree); the code below checks the arguments, fills the kernels' geometry
+// from the shape and the plan, launches what the plan names and sums the slabs
+static_assert(TN_KP == TN_PLAN_KP && T9_MAXW == TN_PLAN_T9_MAXW, "tn_plan.h plans for the kernels of this file");
+
+// the argument checks of every weight-gradient entry point (and of frhip_wgrad_plan), dtype first
+static int tn_check(const TnShape& sh, const char* who, bool transform) {
+    if (const int rc = by_dtype(sh.dtype, who, [](auto) { return FRHIP_OK; })) return rc;
+    const int es = sh.es(), epv = 16 / es;
+    if (sh.n <= 0 || sh.c <= 0 || sh.kc <= 0 || (sh.c % epv) || (sh.ldp % epv) || sh.ldp < sh.kc) {
+        set_error("%s: unsupported shape c=%d kc=%d ldp=%d (c and ldp must be multiples of %d, ldp >= kc)", who, sh.c, sh.kc, sh.ldp, epv);
+        return FRHIP_EINVAL;
+    }
+    const long long pb = sh.M() * sh.ldp * es, qb = 1LL * sh.n * sh.h * sh.w * sh.c * es;
+    if (pb > 0x7fffffffLL || qb > 0x7fffffffLL) { set_error("%s: tensor exceeds the 2 GiB buffer window", who); return FRHIP_EINVAL; }
+    if (transform && !(tn_taps9_ok(sh, g_tn_taps9) && (sh.c % 64) == 0)) {
+        set_error("%s: operand transform needs the nine-tap kernel (bf16 3x3 stride 1, c %% 64 == 0)", who);
+        return FRHIP_EINVAL;
+    }
+    if (sh.out_elems() > 0x7fffffffULL) { set_error("%s: output too large", who); return FRHIP_EINVAL; }
+    return FRHIP_OK;
 }
 
-// Decide where the K splits put their results: private slabs in the caller's workspace (plain stores + one
-// deterministic reduce pass) when there is more than one split, else (one split) straight into `out`.
-static float* tn_pick_dst(TnGeom& g, float* out, int splits, size_t out_elems, float* ws, size_t ws_bytes) {
-    g.slab_stride = 0;
-    // same-address fp32 atomics from hundreds of K splits serialise in L2 (75 us for 500 splits of a 147 KB tile);
-    // slabs + a grouped reduce pass cost two streaming passes over splits * out bytes instead
-    if (splits > 1 && ws && (out_elems % 4) == 0 &&
-        (size_t)splits * out_elems * sizeof(float) <= ws_bytes) {
-        g.slab_stride = (int)out_elems;
-        return ws;
-    }
-    return out;
+static TnGeom tn_geom(const TnShape& sh, const TnPlan& pl, const float* xf_scale = nullptr, const float* xf_shift = nullptr) {
+    TnGeom g;
+    g.H = sh.h; g.W = sh.w; g.C = sh.c; g.R = sh.r; g.S = sh.s; g.stride = sh.stride; g.pad = sh.pad;
+    g.Ho = sh.ho(); g.Wo = sh.wo();
+    g.M = (int)sh.M(); g.Kc = sh.kc; g.ldp = sh.ldp;
+    g.p_bytes = (uint32_t)(sh.M() * sh.ldp * sh.es()); g.q_bytes = (uint32_t)(1LL * sh.n * sh.h * sh.w * sh.c * sh.es());
+    g.d_howo = make_fastdiv((uint32_t)(g.Ho * g.Wo)); g.d_wo = make_fastdiv((uint32_t)g.Wo);
+    g.adv_n = TN_KP / (g.Ho * g.Wo); g.adv_ho = (TN_KP % (g.Ho * g.Wo)) / g.Wo; g.adv_wo = TN_KP % g.Wo;
+    g.ksteps = pl.ksteps; g.ksteps_per_split = pl.ksteps_per_split;
+    g.slab_stride = pl.store == TN_STORE_OUT ? 0 : (int)pl.out_elems;
+    g.xf_scale = xf_scale; g.xf_shift = xf_shift; g.mask_tab = nullptr; g.mask_period = 0;
+    return g;
 }
 
-static int tn_finish(const TnGeom& g, float* out, int splits, size_t out_elems, float* ws, hipStream_t stream) {
-    if (!g.slab_stride) return FRHIP_OK;
-    const size_t n4 = out_elems / 4;
-    int blocks = (int)((n4 + 255) / 256); if (blocks > 2048) blocks = 2048;
-    // one pass while it has enough blocks to stream (or few slabs); else a two-level tree: groups of slabs first
-    int groups = 1;
-    while (splits > 32 * groups && blocks * groups < 512) groups *= 2;
-    if (groups > 1) {
-        const int per_group = (splits + groups - 1) / groups;
-        groups = (splits + per_group - 1) / per_group;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks, groups), dim3(256), 0, stream, ws, splits, per_group,
-                           out_elems, (float*)nullptr, n4, 0);
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks, 1), dim3(256), 0, stream, ws, groups, groups,
-                           (size_t)per_group * out_elems, out, n4, 1);
-    } else {
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks, 1), dim3(256), 0, stream, ws, splits, splits, out_elems, out, n4, 1);
+// the nine-tap instantiations, each named here and nowhere else; a plan that wants the lane-mask table runs its twin without when the
+// table cannot be had now (t9_mask_table)
+static int tn_taps9_run(const TnPlan& pl, TnGeom& g, const void* p, const void* q, float* dst, hipStream_t stream) {
+    const bool table = pl.table && t9_mask_table(g, stream);
+    switch (100 * pl.transform + 10 * table + pl.stages) {
+    case 103: return tn_taps9_launch<1, 4, 4, 1, true, 3, 128>(g, p, q, dst, pl.splits, stream);
+    case 102: return tn_taps9_launch<1, 4, 4, 1, true>(g, p, q, dst, pl.splits, stream);
+    case 14: return tn_taps9_launch<1, 4, 4, 1, false, 4, 96, true>(g, p, q, dst, pl.splits, stream);
+    case 13: return tn_taps9_launch<1, 4, 4, 1, false, 3, 128, true>(g, p, q, dst, pl.splits, stream);
+    case 12: return tn_taps9_launch<1, 4, 4, 1, false, 2, T9_QROWS, true>(g, p, q, dst, pl.splits, stream);
+    case 4: return tn_taps9_launch<1, 4, 4, 1, false, 4, 96>(g, p, q, dst, pl.splits, stream);
+    case 3: return tn_taps9_launch<1, 4, 4, 1, false, 3, 128>(g, p, q, dst, pl.splits, stream);
+    case 2: return tn_taps9_launch<1, 4, 4, 1>(g, p, q, dst, pl.splits, stream);
+    default: set_error("igemm_tn(taps9): no instantiation for %d stages", pl.stages); return FRHIP_EINVAL;
     }
+}
+
+// Sums the plan's K-split slabs into `out`.  Same-address fp32 atomics from hundreds of K splits serialise in L2 (75 us for 500 splits of
+// a 147 KB tile); slabs + a grouped reduce pass cost two streaming passes over splits * out bytes instead.  Groups of slabs are summed
+// first, in place and in the writer's layout, by the generic kernel (two-level tree); the final level adds to `out`: the generic kernel
+// again, or slab9_final_kernel for the nine-tap and rows kernels, whose slabs are in their writer's layout (see tn_taps9_kernel) and are
+// converted to dw[co][tap][ci] here
+static int tn_reduce(const TnPlan& pl, float* out, float* ws, int kc, int c, hipStream_t stream) {
+    if (!pl.groups) return FRHIP_OK;
+    const size_t n4 = pl.out_elems / 4;
+    int count = pl.splits; size_t step = pl.out_elems;      // slabs in front of the final level, and their distance
+    if (pl.groups > 1) {
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3(pl.blocks, pl.groups), dim3(256), 0, stream, ws, pl.splits, pl.per_group,
+                           pl.out_elems, (float*)nullptr, n4, 0);
+        count = pl.groups; step = (size_t)pl.per_group * pl.out_elems;
+    }
+    if (pl.family == TN_TAPS9 || pl.family == TN_ROWS) {
+        hipLaunchKernelGGL(slab9_final_kernel, dim3(pl.blocks), dim3(256), 0, stream, ws, count, step, out, kc / 4, c);
+        return check_launch("igemm_tn(nine-tap slab reduce)");
+    }
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3(pl.blocks, 1), dim3(256), 0, stream, ws, count, count, step, out, n4, 1);
     return check_launch("igemm_tn(slab reduce)");
-}
-
-// nine-tap kernel: its slabs are in the writer's layout (see tn_taps9_kernel); groups of slabs are pre-summed in that layout
-// by the generic kernel, the final level converts to dw[co][tap][ci]
-static int t9_finish(const TnGeom& g, float* out, int splits, size_t out_elems, float* ws, hipStream_t stream) {
-    if (!g.slab_stride) return FRHIP_OK;
-    const size_t n4 = out_elems / 4;
-    int blocks = (int)((n4 + 255) / 256); if (blocks > 2048) blocks = 2048;
-    int groups = 1;
-    while (splits > 32 * groups && blocks * groups < 512) groups *= 2;
-    int count = splits; size_t step = out_elems;
-    if (groups > 1) {
-        const int per_group = (splits + groups - 1) / groups;
-        groups = (splits + per_group - 1) / per_group;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks, groups), dim3(256), 0, stream, ws, splits, per_group,
-                           out_elems, (float*)nullptr, n4, 0);
-        count = groups; step = (size_t)per_group * out_elems;
-    }
-    hipLaunchKernelGGL(slab9_final_kernel, dim3(blocks), dim3(256), 0, stream, ws, count, step, out, g.Kc / 4, g.C);
-    return check_launch("igemm_tn(nine-tap slab reduce)");
-}
-
-static bool t9_applicable(int dtype, int w, int c, int r, int s, int stride, int pad, long long M, int ldp) {
-    const int es = 2;
-    return g_tn_taps9 && dtype == FRHIP_DT_BF16 && r == 3 && s == 3 && stride == 1 && pad == 1 && w <= T9_MAXW &&
-           1LL * (M + 64 + 2LL * w + 2) * (ldp > c ? ldp : c) * es < 0x7fffffffLL;
-}
-
-static bool r14_applicable(int dtype, int h, int w, int c, int kc, int r, int s, int stride, int pad, long long M, int ldp) {
-    return t9_applicable(dtype, w, c, r, s, stride, pad, M, ldp) && h == 14 && w == 14 && (c % 64) == 0 && (kc % 64) == 0;
-}
-// K split of the rows kernel over images: whole rounds of one workgroup per CU; the epilogue (nine store passes of 36 KB per wave) costs
-// about two images.  Sets g.ksteps (= images) / ksteps_per_split and returns the split count.
-static int r14_plan(TnGeom& g, int n, int splits) {
-    const long long tiles = 1LL * (g.Kc / 64) * (g.C / 64);
-    int best = 1; double best_t = 1e30;
-    for (int sp = 1; sp <= n && sp <= 1024; ++sp) {
-        const long long rounds = (tiles * sp + 255) / 256;
-        const double t = (double)rounds * ((double)((n + sp - 1) / sp) + 2.0);
-        if (t < best_t * 0.98) { best_t = t; best = sp; }
-    }
-    int sp = splits > 0 ? splits : best;
-    if (sp > n) sp = n;
-    const int per = (n + sp - 1) / sp;
-    g.ksteps = n; g.ksteps_per_split = per;
-    return (n + per - 1) / per;
 }
 
 static int tn_run(int dtype, const void* p, const void* q, float* out, int n, int h, int w, int c, int kc, int ldp,
                   int r, int s, int stride, int pad, int splits, float* ws, size_t ws_bytes, hipStream_t stream,
                   const char* who, bool overwrite = false, const float* xf_scale = nullptr, const float* xf_shift = nullptr) {
-    if (const int rc = by_dtype(dtype, who, [](auto) { return FRHIP_OK; })) return rc;
-    const int es = dtype == FRHIP_DT_BF16 ? 2 : 4;
-    const int epv = 16 / es;
-    if (n <= 0 || c <= 0 || kc <= 0 || (c % epv) || (ldp % epv) || ldp < kc) {
-        set_error("%s: unsupported shape c=%d kc=%d ldp=%d (c and ldp must be multiples of %d, ldp >= kc)", who, c, kc, ldp, epv);
-        return FRHIP_EINVAL;
-    }
-    TnGeom g;
-    g.H = h; g.W = w; g.C = c; g.R = r; g.S = s; g.stride = stride; g.pad = pad;
-    g.Ho = (h + 2 * pad - r) / stride + 1; g.Wo = (w + 2 * pad - s) / stride + 1;
-    const long long M = 1LL * n * g.Ho * g.Wo;
-    const long long pb = M * ldp * es, qb = 1LL * n * h * w * c * es;
-    if (pb > 0x7fffffffLL || qb > 0x7fffffffLL) { set_error("%s: tensor exceeds the 2 GiB buffer window", who); return FRHIP_EINVAL; }
-    g.M = (int)M; g.Kc = kc; g.ldp = ldp;
-    g.p_bytes = (uint32_t)pb; g.q_bytes = (uint32_t)qb;
-    g.d_howo = make_fastdiv((uint32_t)(g.Ho * g.Wo)); g.d_wo = make_fastdiv((uint32_t)g.Wo);
-    g.adv_n = TN_KP / (g.Ho * g.Wo);
-    g.adv_ho = (TN_KP % (g.Ho * g.Wo)) / g.Wo;
-    g.adv_wo = TN_KP % g.Wo;
-    g.ksteps = (g.M + TN_KP - 1) / TN_KP;
-    g.slab_stride = 0;
-    g.xf_scale = xf_scale; g.xf_shift = xf_shift;
-    g.mask_tab = nullptr; g.mask_period = 0;
-    if (xf_scale && !(t9_applicable(dtype, w, c, r, s, stride, pad, M, ldp) && (c % 64) == 0)) {
-        set_error("%s: operand transform needs the nine-tap kernel (bf16 3x3 stride 1, c %% 64 == 0)", who);
-        return FRHIP_EINVAL;
-    }
-    const int taps = r * s;
-    const size_t out_elems = (size_t)kc * taps * c;
-    if (out_elems > 0x7fffffffULL) { set_error("%s: output too large", who); return FRHIP_EINVAL; }
+    const TnShape sh{dtype, n, h, w, c, kc, ldp, r, s, stride, pad};
+    if (const int rc = tn_check(sh, who, xf_scale != nullptr)) return rc;
+    const TnPlan pl = tn_plan(sh, splits, ws != nullptr, ws_bytes, overwrite, xf_scale != nullptr, g_tn_taps9);
+    TnGeom g = tn_geom(sh, pl, xf_scale, xf_shift);
+    float* dst = pl.store == TN_STORE_SLABS ? ws : out;
     int rc;
-    // The nine-tap kernel covers every 3x3/s1/p1 bf16 layer (g_tn_taps9: 0 off, 1/2 on).
-    if (!xf_scale && ws && r14_applicable(dtype, h, w, c, kc, r, s, stride, pad, M, ldp)) {
-        TnGeom gi = g;
-        int sp = r14_plan(gi, n, splits);
-        float* dst = tn_pick_dst(gi, out, sp, out_elems, ws, ws_bytes);
-        if (gi.slab_stride) {
-            rc = tn_rows14_launch(gi, p, q, dst, sp, stream);
-            return rc ? rc : t9_finish(gi, out, sp, out_elems, ws, stream);
+    switch (pl.family) {
+    case TN_ROWS: rc = tn_rows14_launch(g, p, q, dst, pl.splits, stream); break;
+    case TN_TAPS9: rc = tn_taps9_run(pl, g, p, q, dst, stream); break;
+    default:        // per-tap; the only family with out = result
+        if (pl.clear_out && hipMemsetAsync(out, 0, pl.out_elems * sizeof(float), stream) != hipSuccess) {
+            set_error("%s: cannot clear the output", who); rc = FRHIP_ELAUNCH; break;
         }
-    }
-    if (t9_applicable(dtype, w, c, r, s, stride, pad, M, ldp)) {
-        const long long tiles = 1LL * ((kc + 63) / 64) * ((c + 63) / 64);
-        const int slots = 256;                                                  // one workgroup per CU
-        int best = 1; double best_t = 1e30;
-        const int max_splits = g.ksteps / 8 > 0 ? g.ksteps / 8 : 1;
-        for (int sp = 1; sp <= max_splits && sp <= 1024; ++sp) {
-            const long long rounds = (tiles * sp + slots - 1) / slots;
-            const double t = (double)rounds * ((double)g.ksteps / sp + 8.0);       // epilogue ~ 8 K steps (nine store passes)
-            if (t < best_t * 0.98) { best_t = t; best = sp; }
-        }
-        if (splits <= 0) splits = best;
-        if (splits > g.ksteps) splits = g.ksteps;
-        splits = (kc % 4 == 0) ? tn_slab_splits(splits, out_elems, ws, ws_bytes) : 1;                 // slab layout packs co in fours
-        g.ksteps_per_split = (g.ksteps + splits - 1) / splits;
-        splits = (g.ksteps + g.ksteps_per_split - 1) / g.ksteps_per_split;
-        float* dst = tn_pick_dst(g, out, splits, out_elems, ws, ws_bytes);
-        const bool deep = 64 + 2 * w + 2 <= 128;      // three stages of a 128-row window
-        // W <= 14: a 96-row window, 20-KB stages -- FOUR fit the co-resident tile's 82-KB request, so an operand load has three K steps to land
-        const bool deep4 = deep && 64 + 2 * w + 2 <= 96 && !xf_scale;
-        if (xf_scale) rc = deep ? tn_taps9_launch<1, 4, 4, 1, true, 3, 128>(g, p, q, dst, splits, stream)
-                                : tn_taps9_launch<1, 4, 4, 1, true>(g, p, q, dst, splits, stream);
-        else if (g.Ho == g.H && g.Wo == g.W && t9_mask_table(g, stream))
-            rc = deep4 ? tn_taps9_launch<1, 4, 4, 1, false, 4, 96, true>(g, p, q, dst, splits, stream)
-               : deep ? tn_taps9_launch<1, 4, 4, 1, false, 3, 128, true>(g, p, q, dst, splits, stream)
-                      : tn_taps9_launch<1, 4, 4, 1, false, 2, T9_QROWS, true>(g, p, q, dst, splits, stream);
-        else rc = deep4 ? tn_taps9_launch<1, 4, 4, 1, false, 4, 96>(g, p, q, dst, splits, stream)
-                : deep ? tn_taps9_launch<1, 4, 4, 1, false, 3, 128>(g, p, q, dst, splits, stream)
-                       : tn_taps9_launch<1, 4, 4, 1>(g, p, q, dst, splits, stream);
-        return rc ? rc : t9_finish(g, out, splits, out_elems, ws, stream);
-    }
-    const bool big = (c * es >= 256) && (kc * es >= 256);
-    if (splits <= 0) {
-        // Split-K heuristic: the grid should fill whole "rounds" of the chip (256 CUs x resident workgroups) with as
-        // few splits as possible -- every extra split adds a full slab of the output tile to store and to reduce, and a
-        // partially filled last round wastes up to a third of the launch.
-        const int bc = (big ? 256 : 128) / es;
-        const long long tiles = 1LL * ((kc + bc - 1) / bc) * ((c + bc - 1) / bc) * taps;
-        const int slots = 256 * (big ? 2 : 4);                 // LDS-limited residency: 2 (64 KB) / 4 (32 KB) per CU
-        const int max_splits = (g.ksteps + 7) / 8 > 0 ? (g.ksteps + 7) / 8 : 1;     // >= 8 K steps per workgroup
-        int best = 1; double best_score = -1.0;
-        for (int sp = 1; sp <= max_splits && sp <= 512; ++sp) {
-            const long long wgs = tiles * sp;
-            const long long rounds = (wgs + slots - 1) / slots;
-            const double fill = (double)wgs / (double)(rounds * slots);
-            // time ~ rounds * (ksteps/sp + epilogue cost in K-step units)
-            const double t = (double)rounds * ((double)g.ksteps / sp + 6.0);
-            const double score = 1.0 / t;
-            if (score > best_score * 1.02 || best_score < 0) { best_score = score; best = sp; }
-            (void)fill;
-        }
-        splits = best;
-    }
-    if (splits > g.ksteps) splits = g.ksteps;
-    splits = tn_slab_splits(splits, out_elems, ws, ws_bytes);
-    g.ksteps_per_split = (g.ksteps + splits - 1) / splits;
-    splits = (g.ksteps + g.ksteps_per_split - 1) / g.ksteps_per_split;
-    if (overwrite && splits == 1) {
-        // out = result (not +=) and a single K split: the "slab" store path with slab 0 = out itself -- plain coalesced stores,
-        // no zero fill by the caller and no fp32 atomic read-modify-write pass over the output (the head's 250-MB dW)
-        g.slab_stride = (int)out_elems;
-        return by_dtype(dtype, who, [&](auto t) {
+        rc = by_dtype(dtype, who, [&](auto t) {
             typedef decltype(t) T;
-            return big ? tn_launch<T, 256>(g, p, q, out, taps, 1, stream) : tn_launch<T, 128>(g, p, q, out, taps, 1, stream);
+            return (pl.family == TN_TAP256 ? tn_launch<T, 256> : tn_launch<T, 128>)(g, p, q, dst, r * s, pl.splits, stream);
         });
     }
-    if (overwrite && hipMemsetAsync(out, 0, out_elems * sizeof(float), stream) != hipSuccess) {
-        set_error("%s: cannot clear the output", who);
-        return FRHIP_ELAUNCH;
-    }
-    float* dst = tn_pick_dst(g, out, splits, out_elems, ws, ws_bytes);
-    rc = by_dtype(dtype, who, [&](auto t) {
-        typedef decltype(t) T;
-        return big ? tn_launch<T, 256>(g, p, q, dst, taps, splits, stream) : tn_launch<T, 128>(g, p, q, dst, taps, splits, stream);
-    });
-    return rc ? rc : tn_finish(g, out, splits, out_elems, ws, stream);
+    return rc ? rc : tn_reduce(pl, out, ws, kc, c, stream);
 }
 
 
@@ -1315,7 +1204,7 @@ extern "C" int frhip_conv_wgrad(int dtype, const void* dy, const void* x, float*
 
 // ---- chained weight gradients (rows kernel): launch i sums the K-split slabs of launch i - 1 in its prologue ----------------------
 extern "C" int frhip_conv_wgrad_chain_ok(int dtype, int n, int h, int w, int c, int k, int r, int s, int stride, int pad) {
-    return (n >= 2 && frhip::r14_applicable(dtype, h, w, c, k, r, s, stride, pad, 1LL * n * h * w, k)) ? 1 : 0;
+    return (n >= 2 && tn_rows_ok(TnShape{dtype, n, h, w, c, k, k, r, s, stride, pad}, g_tn_taps9)) ? 1 : 0;
 }
 
 extern "C" int frhip_conv_wgrad_chain(int dtype, const void* dy, const void* x, int n, int h, int w, int c, int k,
@@ -1330,30 +1219,35 @@ extern "C" int frhip_conv_wgrad_chain(int dtype, const void* dy, const void* x, 
         set_error("frhip_conv_wgrad_chain: bad previous-launch descriptor (its slabs must not be this launch's)");
         return FRHIP_EINVAL;
     }
-    TnGeom g;
-    g.H = h; g.W = w; g.C = c; g.R = 3; g.S = 3; g.stride = 1; g.pad = 1; g.Ho = h; g.Wo = w;
-    const long long M = 1LL * n * h * w;
-    g.M = (int)M; g.Kc = k; g.ldp = k;
-    g.p_bytes = (uint32_t)(M * k * 2); g.q_bytes = (uint32_t)(M * c * 2);
-    g.d_howo = make_fastdiv((uint32_t)(h * w)); g.d_wo = make_fastdiv((uint32_t)w);
-    g.adv_n = g.adv_ho = g.adv_wo = 0;
-    g.xf_scale = g.xf_shift = nullptr; g.mask_tab = nullptr; g.mask_period = 0;
-    const int sp = r14_plan(g, n, 0);
-    const size_t out_elems = (size_t)k * 9 * c;
-    if (sp < 2 || (size_t)sp * out_elems * sizeof(float) > slab_bytes) {
-        set_error("frhip_conv_wgrad_chain: %d K splits of %zu bytes do not fit the slab buffer", sp, out_elems * sizeof(float));
+    const TnShape sh{dtype, n, h, w, c, k, k, 3, 3, 1, 1};
+    const TnPlan pl = tn_plan_rows(sh, 0);
+    if (pl.splits < 2 || tn_slab_splits(pl.splits, pl.out_elems, true, true, slab_bytes) != pl.splits) {
+        set_error("frhip_conv_wgrad_chain: %d K splits of %zu bytes do not fit the slab buffer", pl.splits, pl.out_elems * sizeof(float));
         return FRHIP_EINVAL;
     }
-    g.slab_stride = (int)out_elems;
     R14Prev prev{prev_slabs, prev_dw, prev_splits > 0 ? prev_splits : 0, (size_t)prev_k * 9 * prev_c, prev_k / 4, prev_c};
-    *splits_out = sp;
-    return tn_rows14_launch(g, dy, x, slabs, sp, stream, prev);
+    *splits_out = pl.splits;
+    return tn_rows14_launch(tn_geom(sh, pl), dy, x, slabs, pl.splits, stream, prev);
 }
 
 extern "C" int frhip_conv_wgrad_chain_finish(float* dw, float* slabs, int k, int c, int splits, hipStream_t stream) {
     if (!dw || !slabs || k <= 0 || c <= 0 || (k % 4) || splits <= 0) { set_error("frhip_conv_wgrad_chain_finish: bad descriptor"); return FRHIP_EINVAL; }
-    TnGeom g; g.Kc = k; g.C = c; g.slab_stride = k * 9 * c;
-    return t9_finish(g, dw, splits, (size_t)k * 9 * c, slabs, stream);
+    TnPlan pl{};
+    pl.family = TN_ROWS; pl.splits = splits; pl.store = TN_STORE_SLABS; pl.out_elems = (size_t)k * 9 * c;
+    tn_reduce_tree(pl);
+    return tn_reduce(pl, dw, slabs, k, c, stream);
+}
+
+extern "C" int frhip_wgrad_plan(int dtype, int n, int h, int w, int c, int kc, int ldp, int r, int s, int stride, int pad, int splits,
+                                int have_workspace, size_t workspace_bytes, int overwrite, int transform, int* plan_out) {
+    // the plan tn_run would launch for these arguments, read-only: no device is touched
+    const TnShape sh{dtype, n, h, w, c, kc, ldp, r, s, stride, pad};
+    if (const int rc = tn_check(sh, "frhip_wgrad_plan", transform != 0)) return rc;
+    if (!plan_out) { set_error("frhip_wgrad_plan: plan_out required"); return FRHIP_EINVAL; }
+    const TnPlan pl = tn_plan(sh, splits, have_workspace != 0, workspace_bytes, overwrite != 0, transform != 0, g_tn_taps9);
+    const int fields[8] = {pl.family, pl.inst(), pl.splits, pl.ksteps, pl.ksteps_per_split, pl.store, pl.groups, pl.per_group};
+    for (int i = 0; i < 8; ++i) plan_out[i] = fields[i];
+    return FRHIP_OK;
 }
 
 extern "C" int frhip_head_dw_ok(int dtype, int n, int classes, int d) {
@@ -1386,7 +1280,7 @@ extern "C" int frhip_gemm_tn(int dtype, const void* p, const void* q, float* out
 }
 
 extern "C" int frhip_conv_wgrad_bnrelu_fusable(int dtype, int n, int h, int w, int c, int k, int r, int s, int stride, int pad) {
-    return (frhip::t9_applicable(dtype, w, c, r, s, stride, pad, 1LL * n * h * w, k) && (c % 64) == 0) ? 1 : 0;
+    return (tn_taps9_ok(TnShape{dtype, n, h, w, c, k, k, r, s, stride, pad}, g_tn_taps9) && (c % 64) == 0) ? 1 : 0;
 }
 
 extern "C" int frhip_conv_wgrad_bnrelu(int dtype, const void* dy, const void* x, const float* in_scale, const float* in_shift,

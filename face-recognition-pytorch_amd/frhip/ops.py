@@ -172,6 +172,18 @@ def conv_wgrad(dy, x, dw, r, s, stride, pad, splits=0):
     return dw
 
 
+WGRAD_FAMILIES = ("tap128", "tap256", "taps9", "rows")
+
+
+def wgrad_plan(dtype, n, h, w, c, kc, ldp, r, s, stride, pad, splits=0, workspace_bytes=WORKSPACE_BYTES, overwrite=False, transform=False):
+    """(family, instantiation, splits, ksteps, ksteps_per_split, store, reduce groups, slabs per group) of the weight-gradient launch with
+    these arguments (frhip_wgrad_plan; workspace_bytes None = no workspace).  Touches no device."""
+    plan = (ctypes.c_int * 8)()
+    check(lib().frhip_wgrad_plan(dtype, n, h, w, c, kc, ldp, r, s, stride, pad, splits, workspace_bytes is not None, workspace_bytes or 0,
+                                 int(overwrite), int(transform), plan), "frhip_wgrad_plan")
+    return tuple(plan)
+
+
 CHAIN_SLAB_BYTES = 128 << 20
 _CHAIN_SLABS = {}
 

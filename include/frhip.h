@@ -139,6 +139,17 @@ int frhip_conv_wgrad_chain(int dtype, const void* dy, const void* x, int n, int 
                            size_t slab_bytes, float* prev_dw, const float* prev_slabs, int prev_k, int prev_c, int prev_splits,
                            int* splits_out, frhip_stream_t stream);
 int frhip_conv_wgrad_chain_finish(float* dw, float* slabs, int k, int c, int splits, frhip_stream_t stream);
+/* Read-only query: the launch plan of a weight gradient, as frhip_conv_wgrad (ldp = k), frhip_gemm_tn / _overwrite (h = w = r = s = stride
+ * = 1, pad = 0, n = m) and frhip_conv_wgrad_bnrelu (transform = 1) would run it with these arguments and the current
+ * frhip_set_wgrad_taps9 switch.  Same argument checks and errors as those entry points; touches no device.  plan_out[8] (host memory):
+ *   [0] kernel family: 0 per-tap with 128-byte rows, 1 per-tap with 256-byte rows, 2 nine-tap, 3 rows (14 x 14 maps)
+ *   [1] nine-tap instantiation, 100 * operand transform + 10 * lane-mask table wanted + window stages (2, 3 or 4); 0 for other families.
+ *       A launch that cannot have the table (inside a stream capture before the table exists) runs the same instantiation without it
+ *   [2] K splits   [3] K steps (64 pixels; rows family: images)   [4] K steps per split
+ *   [5] where the splits store: 0 one split added into dw, 1 one slab of the workspace each, 2 one split that overwrites dw
+ *   [6] reduce groups: 0 no reduce launch, 1 one pass over the slabs, > 1 that many group sums first, then one pass   [7] slabs per group */
+int frhip_wgrad_plan(int dtype, int n, int h, int w, int c, int kc, int ldp, int r, int s, int stride, int pad, int splits,
+                     int have_workspace, size_t workspace_bytes, int overwrite, int transform, int* plan_out);
 /* nn.Linear forward with its epilogue fused (nets/SwinV2.py:16-32 Mlp, :150-176 qkv / proj): out[m][n] = a[m][k] . w[n][k] +
  * bias[n] (bias may be NULL), stored in `dtype`; act_out (may be NULL) = gelu(out), exact erf form, of the stored value;
  * stats_partial (may be NULL): per-tile BatchNorm partial sums of `out`, rows = frhip_conv_stat_rows(dtype, m, n, 1,1,k,1,1,1,0) */

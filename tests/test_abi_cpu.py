@@ -50,6 +50,7 @@ def test_unknown_dtype_is_refused_first_in_one_wording():
     names = [name for _, name, params in _abi.prototypes()
              if params and params[0] == "int dtype" and params[-1] == "frhip_stream_t stream"]
     assert len(names) >= 60, names
+    names.append("frhip_wgrad_plan")            # no stream: a read-only query, behind the same guard as the weight gradients it plans
     for name in names:
         args = [2] + [None if t is ctypes.c_void_p else t(0) for t in protos[name][1][1:]]
         rc = getattr(lib, name)(*args)

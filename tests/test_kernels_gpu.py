@@ -772,13 +772,18 @@ def test_dgrad_carries_batchnorm_backward_sums_under_stochastic_depth(case):
         np.testing.assert_allclose(got[i], host[i], rtol=2e-3, atol=2e-3 * scale, err_msg="fused epilogue vs float64, sum %d" % i)
 
 
-@pytest.mark.parametrize("case", [(1, 64, 64), (2, 64, 128), (3, 128, 64), (8, 256, 256), (37, 128, 192), (64, 256, 512)])
-def test_rows_weight_gradient_of_14x14_maps_matches_fp32(case):
+@pytest.mark.parametrize("case", [(1, 64, 64), (2, 64, 128), (3, 128, 64), (8, 256, 256), (37, 128, 192), (64, 256, 512), (3, 64, 64, 2)])
+def test_rows_weight_gradient_of_14x14_maps_matches_fp32(case, monkeypatch):
     """tn_rows14_kernel (one image row per K step, vertical taps reuse fragments in registers): 3x3 / stride-1 weight gradient of
     nn.Conv2d on 14 x 14 maps (/root/reference/nets/resnet.py:23-46, the 256-channel stage) against fp32 autograd arithmetic on the
-    same bf16-rounded operands -- odd image counts (the two-image loop runs a phantom image), one image per K split, rectangular c / k."""
+    same bf16-rounded operands -- odd image counts (the two-image loop runs a phantom image), one image per K split, rectangular c / k.
+    A fourth entry is a workspace of that many slabs, fewer than the rows plan's splits: the layer falls through to the nine-tap kernel."""
     ops = _ops()
-    n, c, k = case
+    n, c, k = case[:3]
+    if len(case) > 3:
+        ws = ops.workspace(torch.device("cuda", 0))[:case[3] * k * 9 * c]
+        monkeypatch.setattr(ops, "workspace", lambda device: ws)
+        assert ops.wgrad_plan(0, n, 14, 14, c, k, k, 3, 3, 1, 1)[0] == 3 and ops.wgrad_plan(0, n, 14, 14, c, k, k, 3, 3, 1, 1, 0, ws.numel() * 4)[0] == 2
     x = q(rnd(901 + n, (n, 14, 14, c)), torch.bfloat16)
     dy = q(rnd(902 + n, (n, 14, 14, k)), torch.bfloat16)
     dw = torch.zeros(k, 3, 3, c, device="cuda")

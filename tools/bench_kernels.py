@@ -99,6 +99,7 @@ for (h, c, k, r, stride) in SHAPES:
         for mode in (0, 1):      # 0 = per-tap gather kernel, 1 = nine-tap kernel where it applies
             lib().frhip_set_wgrad_taps9(mode)
             us = timeit(lambda: ops.conv_wgrad(dy, x, dw, r, r, stride, pad, 0))
-            line += " wgrad[m%d] %6.1fus %5.0fTF |" % (mode, us, flops / us / 1e6)
+            plan = ops.wgrad_plan(0, B, h, h, c, k, k, r, r, stride, pad)
+            line += " wgrad[m%d] %6.1fus %5.0fTF %6s x%-3d |" % (mode, us, flops / us / 1e6, ops.WGRAD_FAMILIES[plan[0]], plan[2])
         lib().frhip_set_wgrad_taps9(1)
     print(line, flush=True)
