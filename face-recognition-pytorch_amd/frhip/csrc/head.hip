@@ -9,7 +9,8 @@
 // Cross-rank steps (all-reduce MAX / SUM of the per-row scalars) are done by the host between these kernels.
 // The other margin modules of the reference (nets/ArcFace.py:5-61 CombinedMarginLoss with interclass filtering and easy_margin,
 // :94-106 CosFace) are compile-time variants of the same epilogue (template arguments MK, FILT of head_epilogue), and so is the per-row
-// margin (MG_ROWS: AdaFace, not in the reference), whose two margins per row come from adaface_margins_kernel below.
+// margin (MG_ROWS: AdaFace and MagFace, not in the reference), whose two margins per row come from adaface_margins_kernel or
+// magface_margins_kernel below; MagFace's gradient through the norms is magface_norm_grad_kernel and l2norm_bwd_norm*_kernel.
 #include "igemm_nt.h"
 #include "margin_shared.h"
 #include "frhip.h"
@@ -112,6 +113,53 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
     for (int d = 1; d < 64; d <<= 1) dot += __shfl_xor(dot, d);
     const float inv = out_scale / norms[row];
     for (int j = lane; j < D; j += 64) dx[(size_t)row * D + j] = (dr[j] - to_f32<T>(hr[j]) * dot) * inv;
+}
+
+// The two kernels above with the gradient of the norm itself folded in (frhip_l2norm_bwd_norm; MagFace, whose margin and regulariser
+// depend on |x|): dx = ((dxhat - xhat <dxhat, xhat>) / norm + dnorm xhat) out_scale, d|x|/dx = xhat.  The tangential part goes through
+// the same operations in the same order as above, so dnorm = 0 gives the bits of frhip_l2norm_bwd.
+__global__ __launch_bounds__(256) void l2norm_bwd_norm512_kernel(const float* __restrict__ dxhat, const bf16_t* __restrict__ xhat,
+                                                                 const float* __restrict__ norms, const float* __restrict__ dnorm,
+                                                                 float* __restrict__ dx, int rows, float out_scale) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const size_t off = (size_t)row * 512 + lane * 8;
+    const f32x4_t a = *reinterpret_cast<const f32x4_t*>(dxhat + off), b = *reinterpret_cast<const f32x4_t*>(dxhat + off + 4);
+    const bf16x8_t h = *reinterpret_cast<const bf16x8_t*>(xhat + off);
+    float hv[8], dot = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) hv[e] = (float)h[e];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) dot += a[e] * hv[e] + b[e] * hv[4 + e];
+    dot = wave_sum(dot);
+    const float inv = out_scale / norms[row], radial = dnorm[row] * out_scale;
+    f32x4_t oa, ob;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        oa[e] = (a[e] - hv[e] * dot) * inv + hv[e] * radial;
+        ob[e] = (b[e] - hv[4 + e] * dot) * inv + hv[4 + e] * radial;
+    }
+    *reinterpret_cast<f32x4_t*>(dx + off) = oa;
+    *reinterpret_cast<f32x4_t*>(dx + off + 4) = ob;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void l2norm_bwd_norm_kernel(const float* __restrict__ dxhat, const T* __restrict__ xhat,
+                                                              const float* __restrict__ norms, const float* __restrict__ dnorm,
+                                                              float* __restrict__ dx, int rows, int D, float out_scale) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const float* dr = dxhat + (size_t)row * D;
+    const T* hr = xhat + (size_t)row * D;
+    float dot = 0.f;
+    for (int j = lane; j < D; j += 64) dot += dr[j] * to_f32<T>(hr[j]);
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) dot += __shfl_xor(dot, d);
+    const float inv = out_scale / norms[row], radial = dnorm[row] * out_scale;
+    for (int j = lane; j < D; j += 64) {
+        const float h = to_f32<T>(hr[j]);
+        dx[(size_t)row * D + j] = (dr[j] - h * dot) * inv + h * radial;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -624,6 +672,55 @@ __global__ __launch_bounds__(1024) void adaface_margins_kernel(const float* __re
     }
 }
 
+// Guard band of frhip_magface_norm_grad's test for "the clip of u bound": where it did, the forward kernel stored s cosf(eps) or its
+// negative, and the cosine read back as z / s is within one ulp (6e-8) of that; two ulps of 1 cover it.  Rows whose u lies within
+// ~0.22 eps inside the clip are taken for clipped as well (sin(u) ~ eps there: the term dropped is that small).
+constexpr float MAGFACE_CLIP_BAND = 2.4e-7f;
+
+// MagFace's per-row margins and its regulariser from the embedding norms of the global batch (frhip_magface_margins in frhip.h).  ONE
+// block like the kernel above; reg is summed in float64 in an order that depends on n alone, so every rank gets the same bits from the
+// same gathered norms.
+__global__ __launch_bounds__(1024) void magface_margins_kernel(const float* __restrict__ norms, int n, double l_a, double u_a, double l_m,
+                                                               double u_m, float* __restrict__ m_ang, float* __restrict__ m_add,
+                                                               float* __restrict__ reg) {
+    __shared__ double red[16];
+    const double slope = (u_m - l_m) / (u_a - l_a), inv_ua2 = 1.0 / (u_a * u_a);
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const double a = fmin(fmax((double)norms[i], l_a), u_a);
+        m_ang[i] = (float)(l_m + slope * (a - l_a));
+        m_add[i] = 0.f;
+        acc += a * inv_ua2 + 1.0 / a;
+    }
+    const double sum = block_sum_f64(acc, red);
+    if (threadIdx.x == 0) reg[0] = (float)(sum / (double)n);
+}
+
+// d loss / d norm of every row of the global batch (frhip_magface_norm_grad in frhip.h), from what the forward pass left per row: the
+// owner's target logit (the entry above -inf among the ranks' packed blocks) gives cos(u), the global row max / sum-exp give q.
+__global__ __launch_bounds__(256) void magface_norm_grad_kernel(const float* __restrict__ norms, const float* __restrict__ packed, int ws,
+                                                                int n, const float* __restrict__ rowmax, const float* __restrict__ rowsum,
+                                                                float s, float eps, double l_a, double u_a, double l_m, double u_m,
+                                                                double lambda_g, double gscale, const float* __restrict__ upstream,
+                                                                double out_scale, float* __restrict__ dnorm) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double a = (double)norms[i];
+    if (!(a > l_a && a < u_a)) { dnorm[i] = 0.f; return; }            // the clamp of the norm binds: margin and regulariser are constants
+    float zt = -INFINITY;
+    for (int r = 0; r < ws; ++r) zt = fmaxf(zt, packed[((size_t)r * n + i) * 3 + 2]);
+    double dce = 0.0;
+    if (zt > -INFINITY) {
+        const float cu = zt / s;                                      // m_add = 0: the target logit is s cos(clamp(u))
+        if (fabsf(cu) < cosf(eps) - MAGFACE_CLIP_BAND) {              // else the clip of u bound (or may have): no gradient to the margin
+            const double q = exp((double)zt - (double)rowmax[i]) / (double)rowsum[i];
+            dce = (double)s * sqrt((1.0 - (double)cu) * (1.0 + (double)cu)) * (1.0 - q) * gscale;
+        }
+    }
+    const double g = dce * (u_m - l_m) / (u_a - l_a) + lambda_g * gscale * (1.0 / (u_a * u_a) - 1.0 / (a * a));
+    dnorm[i] = (float)(g * (upstream ? (double)upstream[0] : 1.0) * out_scale);
+}
+
 }  // namespace frhip
 
 using namespace frhip;
@@ -637,6 +734,38 @@ extern "C" int frhip_adaface_margins(const float* norms, int n, double m, double
     hipLaunchKernelGGL(adaface_margins_kernel, dim3(1), dim3(n > 256 ? 1024 : 256), 0, stream, norms, n, m, h, t_alpha, eps, update,
                        batch_mean, batch_std, m_ang, m_add);
     return check_launch("frhip_adaface_margins");
+}
+
+// the argument checks the two MagFace entry points share; `all_ptrs`: every pointer the entry point requires is non-null
+static int magface_args(const char* who, int n, bool all_ptrs, const char* ptr_names, double l_a, double u_a) {
+    if (n < 1 || !all_ptrs || !(u_a > l_a) || !(l_a > 0.0)) {
+        set_error("%s: needs n >= 1 rows (n=%d), non-null %s, and 0 < l_a < u_a (l_a=%g u_a=%g)", who, n, ptr_names, l_a, u_a);
+        return FRHIP_EINVAL;
+    }
+    return FRHIP_OK;
+}
+
+extern "C" int frhip_magface_margins(const float* norms, int n, double l_a, double u_a, double l_m, double u_m, float* m_ang,
+                                     float* m_add, float* reg, hipStream_t stream) {
+    if (const int rc = magface_args("frhip_magface_margins", n, norms && m_ang && m_add && reg, "norms, m_ang, m_add, reg", l_a, u_a)) return rc;
+    hipLaunchKernelGGL(magface_margins_kernel, dim3(1), dim3(n > 256 ? 1024 : 256), 0, stream, norms, n, l_a, u_a, l_m, u_m, m_ang, m_add,
+                       reg);
+    return check_launch("frhip_magface_margins");
+}
+
+extern "C" int frhip_magface_norm_grad(const float* norms, const float* packed, int world_size, int n, const float* rowmax,
+                                       const float* rowsum, float s, float eps, double l_a, double u_a, double l_m, double u_m,
+                                       double lambda_g, double gscale, const float* upstream, double out_scale, float* dnorm,
+                                       hipStream_t stream) {
+    if (const int rc = magface_args("frhip_magface_norm_grad", n, norms && packed && rowmax && rowsum && dnorm,
+                                    "norms, packed, rowmax, rowsum, dnorm", l_a, u_a)) return rc;
+    if (world_size < 1 || !(s > 0.f) || !(eps > 0.f && eps < 0.5f)) {
+        set_error("frhip_magface_norm_grad: needs world_size >= 1, s > 0 and 0 < eps < 0.5 (ws=%d s=%g eps=%g)", world_size, s, eps);
+        return FRHIP_EINVAL;
+    }
+    hipLaunchKernelGGL(magface_norm_grad_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, norms, packed, world_size, n, rowmax, rowsum,
+                       s, eps, l_a, u_a, l_m, u_m, lambda_g, gscale, upstream, out_scale, dnorm);
+    return check_launch("frhip_magface_norm_grad");
 }
 
 extern "C" int frhip_head_sub_max(void) { return HEAD_SUB_MAX; }
@@ -737,6 +866,20 @@ extern "C" int frhip_l2norm_bwd(int dtype, const float* dxhat, const void* xhat,
         if (dtype == FRHIP_DT_BF16 && d == 512) hipLaunchKernelGGL(l2norm_bwd512_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, dxhat, (const bf16_t*)xhat, norms, dx, rows, out_scale);
         else hipLaunchKernelGGL(l2norm_bwd_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, stream, dxhat, (const T*)xhat, norms, dx, rows, d, out_scale);
         return check_launch("frhip_l2norm_bwd");
+    });
+}
+
+extern "C" int frhip_l2norm_bwd_norm(int dtype, const float* dxhat, const void* xhat, const float* norms, const float* dnorm, float* dx,
+                                     int rows, int d, float out_scale, hipStream_t stream) {
+    return by_dtype(dtype, "frhip_l2norm_bwd_norm", [&](auto t) {
+        typedef decltype(t) T;
+        if (rows < 1 || d < 1 || !dxhat || !xhat || !norms || !dnorm || !dx) {
+            set_error("frhip_l2norm_bwd_norm: needs rows >= 1, d >= 1 (rows=%d d=%d) and non-null dxhat, xhat, norms, dnorm, dx", rows, d);
+            return FRHIP_EINVAL;
+        }
+        if (dtype == FRHIP_DT_BF16 && d == 512) hipLaunchKernelGGL(l2norm_bwd_norm512_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, dxhat, (const bf16_t*)xhat, norms, dnorm, dx, rows, out_scale);
+        else hipLaunchKernelGGL(l2norm_bwd_norm_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, stream, dxhat, (const T*)xhat, norms, dnorm, dx, rows, d, out_scale);
+        return check_launch("frhip_l2norm_bwd_norm");
     });
 }
 

@@ -747,6 +747,21 @@ def l2norm_bwd(dxhat, xhat, norms, out_scale=1.0):
     return dx
 
 
+def l2norm_bwd_norm(dxhat, xhat, norms, dnorm, out_scale=1.0):
+    """l2norm_bwd plus the gradient of the norms themselves (dnorm [rows] fp32): dx = ((dxhat - xhat <dxhat, xhat>) / norm + dnorm xhat)
+    out_scale in one launch (frhip_l2norm_bwd_norm)"""
+    _need_f32("l2norm_bwd_norm", dxhat=dxhat, norms=norms, dnorm=dnorm)
+    _need_cuda("l2norm_bwd_norm", xhat=xhat)
+    rows, d = dxhat.shape
+    if xhat.dtype not in _DT or xhat.shape != dxhat.shape or norms.numel() != rows or dnorm.numel() != rows:
+        raise ValueError("l2norm_bwd_norm: xhat (bfloat16 or float32) must match dxhat %s and norms, dnorm hold one value per row, got %s %s, "
+                         "%d, %d" % (tuple(dxhat.shape), xhat.dtype, tuple(xhat.shape), norms.numel(), dnorm.numel()))
+    dx = torch.empty((rows, d), dtype=torch.float32, device=dxhat.device)
+    check(lib().frhip_l2norm_bwd_norm(dt_of(xhat), _p(dxhat), _p(xhat), _p(norms), _p(dnorm), _p(dx), rows, d, out_scale, _s()),
+          "frhip_l2norm_bwd_norm")
+    return dx
+
+
 def head_dw(dt, ehat, what, wnorm, out_scale=1.0):
     """class-centre gradient d_w [classes, 512] fp32 from dT [n, ldt], the normalised embeddings and centres and the centres' norms in one
     launch (frhip_head_dw), or None when the shape is not served (fp32 mode, d != 512): the caller then runs gemm_tn + l2norm_bwd"""
@@ -803,6 +818,41 @@ def adaface_margins(norms, m, h, t_alpha, eps, batch_mean, batch_std, update):
     check(lib().frhip_adaface_margins(_p(norms), n, m, h, t_alpha, eps, int(bool(update)), _p(batch_mean), _p(batch_std),
                                       _p(out[0]), _p(out[1]), _s()), "frhip_adaface_margins")
     return out[0], out[1]
+
+
+def _need_f32(who, **tensors):
+    _need_cuda(who, **tensors)
+    for nm, t in tensors.items():
+        if t.dtype != torch.float32:
+            raise ValueError("%s: %s must be float32, got %s" % (who, nm, t.dtype))
+
+
+def magface_margins(norms, l_a, u_a, l_m, u_m):
+    """MagFace's per-row margins and regulariser from the embedding norms [n] of the global batch in ONE launch (frhip_magface_margins)
+    -> (m_ang [n], m_add [n] = 0, reg [1] = mean of a / u_a^2 + 1 / a over a = clamp(norms, l_a, u_a)).  No host sync."""
+    _need_f32("magface_margins", norms=norms)
+    n = norms.numel()
+    out = torch.empty((2, n), dtype=torch.float32, device=norms.device)
+    reg = torch.empty((1,), dtype=torch.float32, device=norms.device)
+    check(lib().frhip_magface_margins(_p(norms), n, l_a, u_a, l_m, u_m, _p(out[0]), _p(out[1]), _p(reg), _s()), "frhip_magface_margins")
+    return out[0], out[1], reg
+
+
+def magface_norm_grad(norms, packed, rmax, rsum, s, eps, l_a, u_a, l_m, u_m, lambda_g, gscale, upstream=None, out_scale=1.0):
+    """d loss / d norms [n] of MagFace's loss (frhip_magface_norm_grad): norms [n] of the global batch, packed [ws, n, 3] the
+    head_pack_stats blocks of all ranks, rmax / rsum [n] the global row statistics, gscale = 1 / n, upstream a device scalar or None"""
+    tensors = dict(norms=norms, packed=packed, rowmax=rmax, rowsum=rsum)
+    if upstream is not None:
+        tensors["upstream"] = upstream
+    _need_f32("magface_norm_grad", **tensors)
+    n = norms.numel()
+    if packed.dim() != 3 or packed.shape[1] != n or packed.shape[2] != 3 or rmax.numel() != n or rsum.numel() != n:
+        raise ValueError("magface_norm_grad: packed must be [world_size, %d, 3] and rowmax, rowsum [%d], got %s, %s, %s"
+                         % (n, n, tuple(packed.shape), tuple(rmax.shape), tuple(rsum.shape)))
+    dnorm = torch.empty((n,), dtype=torch.float32, device=norms.device)
+    check(lib().frhip_magface_norm_grad(_p(norms), _p(packed), packed.shape[0], n, _p(rmax), _p(rsum), s, eps, l_a, u_a, l_m, u_m,
+                                        lambda_g, gscale, _p(upstream), out_scale, _p(dnorm), _s()), "frhip_magface_norm_grad")
+    return dnorm
 
 
 def head_sub_max():

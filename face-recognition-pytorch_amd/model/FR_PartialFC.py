@@ -60,9 +60,27 @@ class _NormalizeNormsFn(torch.autograd.Function):
         return ops.l2norm_bwd(g.contiguous().float(), xh, nrm)
 
 
-def normalize_with_norms(x):
-    """-> (F.normalize(x) rows, their norms before normalisation [N], detached)"""
-    return _NormalizeNormsFn.apply(x)
+class _NormalizeNormsGradFn(torch.autograd.Function):
+    """_NormalizeNormsFn whose norms are differentiable (a margin with norms_need_grad, nets.ArcFace.MagFace): the backward pass is ONE
+    launch that folds the norms' gradient into the normalise-backward (frhip_l2norm_bwd_norm)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        from frhip import ops
+        xh, nrm = ops.l2norm_rows(x.contiguous().float(), torch.float32)
+        ctx.save_for_backward(xh, nrm)
+        return xh, nrm
+
+    @staticmethod
+    def backward(ctx, g, gn):
+        from frhip import ops
+        xh, nrm = ctx.saved_tensors
+        return ops.l2norm_bwd_norm(g.contiguous().float(), xh, nrm, gn.contiguous().float())
+
+
+def normalize_with_norms(x, norms_need_grad=False):
+    """-> (F.normalize(x) rows, their norms before normalisation [N]); the norms are detached unless norms_need_grad"""
+    return (_NormalizeNormsGradFn if norms_need_grad else _NormalizeNormsFn).apply(x)
 
 
 class Model(nn.Module):
@@ -127,9 +145,11 @@ class Model(nn.Module):
         if hasattr(self.loss, "prepare"):          # label all-gather + the one sync sampling needs, before the GPU gets busy
             self.loss.prepare(id_, self.opt)
         extra = {}
-        if getattr(getattr(self.loss, "margin_softmax", None), "needs_norms", False):
-            # AdaFace: the head is fed unit rows, so the norms its margins depend on are the ones this normalisation divides by
-            feat, extra["norms"] = normalize_with_norms(self.forward(img))
+        margin = getattr(self.loss, "margin_softmax", None)
+        if getattr(margin, "needs_norms", False):
+            # AdaFace, MagFace: the head is fed unit rows, so the norms its margins depend on are the ones this normalisation divides by;
+            # MagFace sends a gradient back through them
+            feat, extra["norms"] = normalize_with_norms(self.forward(img), bool(getattr(margin, "norms_need_grad", False)))
         else:
             feat = normalize(self.forward(img))
         self.loss.train()

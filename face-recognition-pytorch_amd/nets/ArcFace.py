@@ -8,7 +8,8 @@ autograd node.
 
 `AdaFace(s, m, h, t_alpha)` (Kim et al., CVPR 2022; not in the reference) gives every row its own margin, derived from the norm of that
 row's embedding before normalisation: `forward(logits, labels, norms)`.  It clamps EVERY cosine, so unlike the others it returns a new
-tensor and leaves `logits` untouched.
+tensor and leaves `logits` untouched.  `MagFace(s, m, u_margin, l_a, u_a, lambda_g)` (Meng et al., CVPR 2021; not in the reference) does the
+same with a margin that grows with the norm; its regulariser and the gradient through the norms live in the fused head.
 
 Inside PartialFC the margin is not applied through this `forward`: it lives in the epilogue of the fused cos-theta
 MFMA kernel (frhip_head_fwd / frhip_head_fwd_ex), which only reads the module's constants through `margin_of`, so the
@@ -29,15 +30,22 @@ Margin = collections.namedtuple("Margin", "kind easy s m filter_thr")
 # the batch's norms into margins: scale, clamp width and the device vectors [N] of angular / additive margins (frhip_margin_rows_t).
 AdaMargin = collections.namedtuple("AdaMargin", "s m h t_alpha eps")
 RowMargins = collections.namedtuple("RowMargins", "s eps m_ang m_add")
+# MagFace: the constants of the module (m, u_margin: the margin at norms l_a and u_a; lambda_g: the weight of the regulariser); the kernels
+# take RowMargins as well, filled by frhip_magface_margins
+MagMargin = collections.namedtuple("MagMargin", "s m u_margin l_a u_a lambda_g eps")
 
-SUPPORTED = "ArcFace, CosFace, CombinedMarginLoss (ArcFace m1 == 1, m3 == 0 or CosFace m3 > 0), AdaFace"
+SUPPORTED = "ArcFace, CosFace, CombinedMarginLoss (ArcFace m1 == 1, m3 == 0 or CosFace m3 > 0), AdaFace, MagFace"
 
 
 def margin_of(module):
     """-> Margin of a margin module of this package, read from its attributes NOW (so a later `easy_margin = True` counts, as in
-    the reference, whose modules read their attributes in forward); AdaMargin for AdaFace.  NotImplementedError for any other module."""
+    the reference, whose modules read their attributes in forward); AdaMargin for AdaFace, MagMargin for MagFace.  NotImplementedError
+    for any other module."""
     if isinstance(module, AdaFace):
         return AdaMargin(float(module.s), float(module.m), float(module.h), float(module.t_alpha), float(module.eps))
+    if isinstance(module, MagFace):
+        return MagMargin(float(module.s), float(module.m), float(module.u_margin), float(module.l_a), float(module.u_a),
+                         float(module.lambda_g), float(module.eps))
     if isinstance(module, ArcFace):
         return Margin(ARCFACE, bool(module.easy_margin), float(module.scale), float(module.margin), 0.0)
     if isinstance(module, CosFace):
@@ -191,3 +199,42 @@ class AdaFace(torch.nn.Module):
 def _hip_adaface_margins(norms, mg, batch_mean, batch_std, update):
     from frhip import ops
     return ops.adaface_margins(norms, mg.m, mg.h, mg.t_alpha, mg.eps, batch_mean, batch_std, update)
+
+
+class MagFace(torch.nn.Module):
+    """Magnitude-aware margin (MagFace, Meng et al., CVPR 2021): with a = clip(norm, l_a, u_a), row i's target logit is
+    s cos(clip(theta + m_i, eps, pi - eps)), m_i = m + (u_margin - m) (a_i - l_a) / (u_a - l_a); every cosine is clamped to
+    [-1 + eps, 1 - eps] first and every logit is x s.  The loss gains lambda_g x the mean over the GLOBAL batch of g(a) = a / u_a^2 + 1 / a,
+    and a gradient flows through the norms (margin and regulariser) while l_a < norm < u_a: the norm becomes a quality score.
+    Where theta + m_i passes pi the angle is clipped (the per-row margin kernels' rule), where the official code switches to
+    cos(theta) - m sin(m).  needs_norms / norms_need_grad tell PartialFC / Model to hand differentiable norms over.  No buffers."""
+    kind = "magface"
+    needs_norms = True
+    norms_need_grad = True
+    eps = 1e-3
+
+    def __init__(self, s=64.0, m=0.45, u_margin=0.8, l_a=10.0, u_a=110.0, lambda_g=35.0):
+        super().__init__()
+        self.s, self.m, self.u_margin, self.l_a, self.u_a, self.lambda_g = s, m, u_margin, l_a, u_a, lambda_g
+        self.scale, self.margin = s, m
+
+    def row_margins(self, norms, kernels=None):
+        """norms [N] of the global batch (detached) -> (RowMargins, reg): the per-row margins and the regulariser's value (a tensor of
+        one element, not yet x lambda_g).  ONE launch of frhip_magface_margins, no host synchronisation.  kernels: PartialFC's kernel
+        object (tests swap in a double)."""
+        mg = margin_of(self)
+        norms = norms.detach().reshape(-1).contiguous()
+        fn = kernels.magface_margins if kernels is not None else _hip_magface_margins
+        m_ang, m_add, reg = fn(norms, mg)
+        return RowMargins(mg.s, mg.eps, m_ang, m_add), reg
+
+    def forward(self, logits: torch.Tensor, labels: torch.Tensor, norms: torch.Tensor):
+        """The margin alone, on explicit cosines: -> the scaled logits (a new tensor, like AdaFace.forward), differentiable in `logits`
+        only.  The regulariser and the gradient through the norms live in the fused head (nets.PartialFC); `row_margins` returns the
+        regulariser's value."""
+        return _RowMarginFn.apply(logits, labels, self.row_margins(norms)[0])
+
+
+def _hip_magface_margins(norms, mg):
+    from frhip import ops
+    return ops.magface_margins(norms.float(), mg.l_a, mg.u_a, mg.m, mg.u_margin)

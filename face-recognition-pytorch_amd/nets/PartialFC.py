@@ -20,7 +20,9 @@ What runs where
     triples that every rank merges itself (the reference issues all-reduce MAX, SUM, SUM, :448-459), and ONE
     reduce-scatter of dE issued before the dW GEMM so the two overlap (the reference loops world_size reduce() calls,
     :510-519).  AdaFace alone adds a fifth, small one: an all-gather of the rows' norms ([N] floats), from which every rank derives the
-    same per-row margins and the same running statistics (frhip_adaface_margins, one launch).
+    same per-row margins and the same running statistics (frhip_adaface_margins, one launch).  MagFace gathers the norms the same way
+    (frhip_magface_margins: margins and regulariser in one launch) and returns d loss / d norm of its own rows from the statistics every
+    rank already holds (frhip_magface_norm_grad), with no further collective.
 `conf.subcenters = K` (not in the reference; sub-center ArcFace): every class owns K centres, the table is plane-major [K x num_local, D]
 (centre k of class c in row k * num_local + c), the fused kernels take the maximum over a class's centres on their accumulators and send
 its gradient to the winner alone; sampling, sharding and the collectives stay at class level.  Absent or 1: the calls made before.
@@ -34,8 +36,8 @@ from typing import Callable
 import torch
 from torch import distributed
 
-from .ArcFace import (SUPPORTED as SUPPORTED_MARGINS, AdaFace, AdaMargin, ArcFace, CombinedMarginLoss, CosFace, RowMargins,
-                      is_plain_arcface, margin_of)
+from .ArcFace import (SUPPORTED as SUPPORTED_MARGINS, AdaFace, AdaMargin, ArcFace, CombinedMarginLoss, CosFace, MagFace, MagMargin,
+                      RowMargins, is_plain_arcface, margin_of)
 
 
 import os
@@ -64,6 +66,15 @@ class HipHeadKernels:
     def adaface_margins(self, norms, mg, batch_mean, batch_std, update):
         """-> (m_ang, m_add) [N] from the global batch's norms; update: batch_mean / batch_std are advanced in place first"""
         return self.ops.adaface_margins(norms, mg.m, mg.h, mg.t_alpha, mg.eps, batch_mean, batch_std, update)
+
+    def magface_margins(self, norms, mg):
+        """-> (m_ang, m_add, reg [1]) from the global batch's norms [N]; mg: nets.ArcFace.MagMargin"""
+        return self.ops.magface_margins(norms.float(), mg.l_a, mg.u_a, mg.m, mg.u_margin)
+
+    def magface_norm_grad(self, norms, packed, rmax, rsum, mg, gscale, upstream, out_scale=1.0):
+        """-> d loss / d norms [N] x out_scale; packed [ws, N, 3]: the pack_stats blocks of all ranks, rmax / rsum: the global statistics"""
+        return self.ops.magface_norm_grad(norms.float(), packed, rmax, rsum, mg.s, mg.eps, mg.l_a, mg.u_a, mg.m, mg.u_margin, mg.lambda_g,
+                                          gscale, upstream, out_scale)
 
     def rescale(self, rowsum, local_max, global_max):
         self.ops.head_rescale(rowsum, local_max, global_max)
@@ -178,11 +189,14 @@ class _MarginSoftmaxFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, local_embeddings, weight_activated, labels_i32, kern, s, m, world_size, collectives, margin=None, adaface=None,
-                subcenters=1, sub_out=None):
+                subcenters=1, sub_out=None, magface=None, local_norms=None):
         """adaface: None, or (AdaFace module, this rank's norms [rows]) -- the per-row margins are then derived here, from the norms of
         the global batch in rank order, and `margin` is ignored.
         subcenters = K > 1: weight_activated holds K x classes rows, plane-major; the winning centre of every row's target (int32 [N], -1
-        where another shard owns the row) is appended to the list sub_out"""
+        where another shard owns the row) is appended to the list sub_out
+        magface: None, or the MagFace module, with local_norms = this rank's norms [rows] as a tensor input of the node: margins and
+        regulariser are derived here from the gathered norms, the loss is CE + lambda_g reg, and backward returns the gradient of this
+        rank's norms when they require one"""
         local_embeddings = local_embeddings.contiguous()
         rows, dim = local_embeddings.shape
         if collectives:                                                         # :182 (C1)
@@ -201,6 +215,14 @@ class _MarginSoftmaxFn(torch.autograd.Function):
             rm = module.row_margins(norms, kern)            # ONE launch; advances the running buffers in training mode
             extra, row_vecs = {"margin": rm}, (rm.m_ang, rm.m_add)
             ctx.row_consts = (rm.s, rm.eps)
+        ctx.mag, mag_saved = None, ()
+        if magface is not None:
+            mag = margin_of(magface)
+            own = local_norms.detach().reshape(-1).contiguous()
+            norms = _all_gather_flat(own.new_empty(world_size * rows), own) if collectives else own
+            rm, reg = magface.row_margins(norms, kern)      # ONE launch: both margin vectors and the regulariser
+            extra, row_vecs = {"margin": rm}, (rm.m_ang, rm.m_add)
+            ctx.row_consts = (rm.s, rm.eps)
         if subcenters > 1:                                   # one centre per class: the calls made before sub-centres existed
             zt, rmax, rsum, tsub = kern.forward_stats(ehat, what, labels_i32, s, m, subcenters=subcenters, **extra)
             if sub_out is not None:
@@ -210,24 +232,33 @@ class _MarginSoftmaxFn(torch.autograd.Function):
         if collectives:                                                         # :448, :453, :459 (C3-C5) in one exchange
             mine = kern.pack_stats(zt, labels_i32, rmax, rsum)
             allst = _all_gather_flat(mine.new_empty((world_size * mine.shape[0], mine.shape[1])), mine)
-            rmax, rsum, q = kern.merge_stats(allst.view(world_size, mine.shape[0], mine.shape[1]))
+            allst = allst.view(world_size, mine.shape[0], mine.shape[1])
+            rmax, rsum, q = kern.merge_stats(allst)
         else:
             q = kern.target_prob(zt, labels_i32, rmax, rsum)
         loss = kern.loss(q)
+        if magface is not None:
+            loss = torch.add(loss, reg.to(loss.dtype), alpha=mag.lambda_g)      # CE + lambda_g reg: one one-element launch
+            if ctx.needs_input_grad[13]:
+                # the norm gradient reads every row's target logit from the packed blocks; one rank alone packs its own for that
+                packed = allst if collectives else kern.pack_stats(zt, labels_i32, rmax, rsum).unsqueeze(0)
+                ctx.mag, mag_saved = (mag, local_norms.shape, local_norms.dtype), (norms, packed)
         ctx.kern, ctx.s, ctx.m, ctx.world_size, ctx.collectives, ctx.rows = kern, s, m, world_size, collectives, rows
         ctx.extra = {} if row_vecs else extra
         ctx.sub = {"subcenters": subcenters} if subcenters > 1 else {}
-        ctx.save_for_backward(ehat, enorm, what, wnorm, labels_i32, rmax, rsum, *row_vecs)
+        ctx.save_for_backward(ehat, enorm, what, wnorm, labels_i32, rmax, rsum, *row_vecs, *mag_saved)
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, grad_loss):
         ehat, enorm, what, wnorm, labels_i32, rmax, rsum, *row_vecs = ctx.saved_tensors
+        if ctx.mag is not None:
+            row_vecs, ctx.mag_saved = row_vecs[:2], row_vecs[2:]
         extra = dict({"margin": RowMargins(*ctx.row_consts, *row_vecs)} if row_vecs else ctx.extra, **ctx.sub)
         up = grad_loss.reshape(1).float().contiguous()
         if not ctx.collectives:
             d_e, d_w = ctx.kern.backward(ehat, enorm, what, wnorm, labels_i32, ctx.s, ctx.m, rmax, rsum, ehat.shape[0], up, **extra)
-            return d_e, d_w, None, None, None, None, None, None, None, None, None, None
+            return (d_e, d_w) + (None,) * 11 + (_MarginSoftmaxFn._norm_grad(ctx, rmax, rsum, up, 0, 1.0),)
         # :504-522 (C6): reduce-scatter(SUM) of dE, x world_size (folded into the normalise-backward's scale); issued as soon
         # as dE is enqueued so that it runs beside the dW GEMM
         pending = []
@@ -241,7 +272,17 @@ class _MarginSoftmaxFn(torch.autograd.Function):
         d_local, work = pending[0]
         if work is not None:
             work.wait()
-        return d_local, d_w, None, None, None, None, None, None, None, None, None, None
+        return (d_local, d_w) + (None,) * 11 + (_MarginSoftmaxFn._norm_grad(ctx, rmax, rsum, up, rank, float(ctx.world_size)),)
+
+    @staticmethod
+    def _norm_grad(ctx, rmax, rsum, up, rank, scale):
+        """MagFace: d loss / d (this rank's norms) x scale (the world size, like the embedding gradient), or None.  Every rank evaluates
+        all N rows from the gathered blocks and keeps its slice: no further collective."""
+        if ctx.mag is None:
+            return None
+        (mag, shape, dtype), (norms, packed) = ctx.mag, ctx.mag_saved
+        d_n = ctx.kern.magface_norm_grad(norms, packed, rmax, rsum, mag, 1.0 / norms.numel(), up, out_scale=scale)
+        return d_n[rank * ctx.rows:(rank + 1) * ctx.rows].to(dtype).reshape(shape)
 
 
 class DistCrossEntropyFunc(torch.autograd.Function):
@@ -327,7 +368,7 @@ class _PartialFCBase(torch.nn.Module):
             self.margin_softmax = margin_loss(conf.loss_s, conf.loss_m)
         else:
             raise
-        if not isinstance(self.margin_softmax, (ArcFace, CosFace, CombinedMarginLoss, AdaFace)):
+        if not isinstance(self.margin_softmax, (ArcFace, CosFace, CombinedMarginLoss, AdaFace, MagFace)):
             raise NotImplementedError("the fused head kernel implements the margin modules %s, not %s"
                                       % (SUPPORTED_MARGINS, type(self.margin_softmax).__name__))
         self._kernels = kernels
@@ -528,7 +569,8 @@ class _PartialFCBase(torch.nn.Module):
 
     def forward(self, local_embeddings, local_labels, optimizer, norms=None):
         """norms: this rank's [B] embedding norms BEFORE normalisation, for a margin that derives per-row margins from them (AdaFace,
-        `margin_softmax.needs_norms`); required there, refused elsewhere.  No gradient flows through them."""
+        MagFace: `margin_softmax.needs_norms`); required there, refused elsewhere.  AdaFace takes no gradient through them; MagFace
+        (`margin_softmax.norms_need_grad`) returns d loss / d norms, margin and regulariser, to norms that require a gradient."""
         needs_norms = bool(getattr(self.margin_softmax, "needs_norms", False))
         if needs_norms and norms is None:
             raise ValueError("%s derives its margins from the embedding norms: call forward(local_embeddings, local_labels, optimizer, "
@@ -578,6 +620,8 @@ class _PartialFCBase(torch.nn.Module):
         # AdaFace: its per-row margins are derived inside the autograd node, from the gathered norms; every other margin makes the call
         # it made before per-row margins existed
         tail = (None, (self.margin_softmax, norms)) if isinstance(mg, AdaMargin) else (margin,)
+        if isinstance(mg, MagMargin):                            # the norms are a tensor input of the node: it returns their gradient
+            tail = (None, None, 1, None, self.margin_softmax, norms)
         if ready is not None and ready.numel() == n_global:      # everything label-side was done by prepare()
             return self._margin_softmax(local_embeddings, ready, s, m, collectives, tail)
         n_pos = None
@@ -602,7 +646,7 @@ class _PartialFCBase(torch.nn.Module):
                                           self.world_size, collectives, *tail)
         won = []
         loss = _MarginSoftmaxFn.apply(local_embeddings, self.weight_activated, labels_i32, self.kernels, s, m,
-                                      self.world_size, collectives, *(tail + (None,))[:2], self.subcenters, won)
+                                      self.world_size, collectives, *(tail + (None,))[:2], self.subcenters, won, *tail[4:])
         self.last_target_sub = won[0]
         if self.sub_hits is not None and self.training:
             self._count_sub_hits(labels_i32, won[0])

@@ -279,6 +279,10 @@ int frhip_l2norm_rows(int dtype, const float* x, void* xhat, float* norms, int r
                       frhip_stream_t stream);
 int frhip_l2norm_bwd(int dtype, const float* dxhat, const void* xhat, const float* norms, float* dx,
                      int rows, int d, float out_scale, frhip_stream_t stream);
+/* frhip_l2norm_bwd with the gradient of the norm itself folded in (dnorm [rows] fp32; MagFace):
+ * dx = ((dxhat - xhat <dxhat, xhat>) / norm + dnorm xhat) out_scale.  dnorm = 0 gives the bits of frhip_l2norm_bwd. */
+int frhip_l2norm_bwd_norm(int dtype, const float* dxhat, const void* xhat, const float* norms, const float* dnorm, float* dx,
+                          int rows, int d, float out_scale, frhip_stream_t stream);
 int frhip_head_groups(int num_classes);     /* rows of part_max / part_sum */
 /* fused normalised-GEMM -> clamp -> ArcFace margin -> x s -> per-row max & sum-exp (this shard);
  * labels: int32 shard-relative, -1 = another shard owns the class. */
@@ -339,6 +343,31 @@ typedef struct { float s, eps; const float* m_ang; const float* m_add; } frhip_m
  * batch_mean, batch_std: device scalars (fp32).  n < 2 or a null pointer: FRHIP_EINVAL, nothing is launched. */
 int frhip_adaface_margins(const float* norms, int n, double m, double h, double t_alpha, double eps, int update, float* batch_mean,
                           float* batch_std, float* m_ang, float* m_add, frhip_stream_t stream);
+/* MagFace (not in the reference: Meng et al., CVPR 2021): the margin grows with the embedding's norm and a regulariser rewards large
+ * norms, so the norm becomes a quality score.  With n_i the norm of row i before normalisation, over the global batch of n rows:
+ *   a_i = clamp(n_i, l_a, u_a);  m_ang[i] = l_m + (u_m - l_m) (a_i - l_a) / (u_a - l_a);  m_add[i] = 0;
+ *   reg = (1 / n) sum_i g(a_i),  g(a) = a / u_a^2 + 1 / a;  loss = CE + lambda_g reg, CE being the head's cross-entropy with the
+ *   logits of frhip_margin_rows_t above.  Where theta + m passes pi that is the rows clip, not the official code's cos(theta) - m sin(m).
+ * frhip_magface_margins: ONE launch (one workgroup), no host synchronisation (capturable).  Fills m_ang and m_add (zeros) and writes the
+ * device scalar reg (fp32), summed in float64 in an order fixed by n: the same norms give the same bits on every rank.
+ * n < 1, a null pointer, u_a <= l_a or l_a <= 0: FRHIP_EINVAL, nothing is launched. */
+int frhip_magface_margins(const float* norms, int n, double l_a, double u_a, double l_m, double u_m, float* m_ang, float* m_add,
+                          float* reg, frhip_stream_t stream);
+/* The gradient of that loss through the norms, every one of the n rows of the global batch written:
+ *   dnorm[i] = [l_a < n_i < u_a] (dCE/dm_ang[i] (u_m - l_m) / (u_a - l_a) + lambda_g gscale (1 / u_a^2 - 1 / n_i^2)) upstream out_scale
+ *   dCE/dm_ang[i] = s sin(u_i) (1 - q_i) gscale while the clip of u_i = theta_i + m_ang[i] to [eps, pi - eps] does not bind, else 0, from
+ *   what the forward pass left: cos(u_i) = z_i / s with z_i the row's target logit, sin(u_i) = sqrt(1 - cos^2) >= 0, and
+ *   q_i = exp(z_i - rowmax[i]) / rowsum[i].  A row without a target keeps the regulariser term alone.
+ * packed [world_size][n][3]: the blocks of frhip_head_pack_stats of all ranks (world_size 1: this rank's own); the target logit is the
+ * entry above -inf among a row's third components.  rowmax, rowsum: the GLOBAL row statistics.  gscale = 1 / n.  upstream: device
+ * scalar or NULL (1), as in frhip_head_bwd_dt.  out_scale: the world size across ranks, like the embedding gradient's.
+ * Whether the clip bound is read off the stored logit: it did where |z_i / s| >= cosf(eps) - 2.4e-7.  The forward kernel stores
+ * s cosf(eps) (or its negative) there and z / s returns it within one ulp (6e-8); the band of two ulps of 1 also takes a row whose u
+ * lies within 0.22 eps inside the clip for clipped, where the dropped term is s sin(1.22 eps) (1 - q) gscale at most.
+ * Bad arguments as above, and world_size < 1, s <= 0 or eps outside (0, 0.5): FRHIP_EINVAL, nothing is launched. */
+int frhip_magface_norm_grad(const float* norms, const float* packed, int world_size, int n, const float* rowmax, const float* rowsum,
+                            float s, float eps, double l_a, double u_a, double l_m, double u_m, double lambda_g, double gscale,
+                            const float* upstream, double out_scale, float* dnorm, frhip_stream_t stream);
 /* frhip_head_fwd / frhip_head_bwd_dt with per-row margins: one more instantiation of the same kernel (two floats read per row) */
 int frhip_head_fwd_rows(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
                         int d, const frhip_margin_rows_t* margin, float* part_max, float* part_sum, float* ztarget,
