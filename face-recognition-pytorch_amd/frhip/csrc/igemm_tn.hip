@@ -823,11 +823,16 @@ constexpr int T9_LDS = 83968;
 // in module memory, filled on first use (blocking copy: never inside a stream capture -- a warm-up step comes first).
 constexpr int T9_TAB_GEOMS = 8, T9_TAB_MAXP = 64;
 __device__ unsigned long long g_t9_masks[T9_TAB_GEOMS][T9_TAB_MAXP * 16];
+// keyed by DEVICE too: g_t9_masks is module memory, every device has its own copy at its own address.  Entries are never
+// dropped: a captured graph may hold their addresses (frhip_wgrad_mask_table_period reads the cache, nothing empties it)
+static struct { int device, h, w, period; const unsigned long long* dev; } g_t9_cache[T9_TAB_GEOMS];
+static int g_t9_cached = 0;
+static int g_t9_table = 1;      // frhip_set_wgrad_mask_table: 0 = nine-tap launches never ask for the table
 static bool t9_mask_table(TnGeom& g, hipStream_t stream) {
-    // keyed by DEVICE too: g_t9_masks is module memory, every device has its own copy at its own address
-    static struct { int device, h, w, period; const unsigned long long* dev; } cache[T9_TAB_GEOMS];
-    static int used = 0;
+    auto& cache = g_t9_cache;
+    int& used = g_t9_cached;
     g.mask_tab = nullptr; g.mask_period = 0;
+    if (!g_t9_table) return false;
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) { (void)hipGetLastError(); return false; }
     for (int i = 0; i < used; ++i)
@@ -1192,6 +1197,22 @@ extern "C" int frhip_set_wgrad_taps9(int enabled) {
     const int old = g_tn_taps9;
     if (enabled >= 0) g_tn_taps9 = enabled ? 1 : 0;
     return old;
+}
+
+extern "C" int frhip_set_wgrad_mask_table(int enabled) {
+    // 1 (default): nine-tap launches take the lane-mask table when it can be had; 0: always the twin without; < 0 queries
+    const int old = g_t9_table;
+    if (enabled >= 0) g_t9_table = enabled ? 1 : 0;
+    return old;
+}
+
+extern "C" int frhip_wgrad_mask_table_period(int h, int w) {
+    // period of the table cached for (current device, h, w), 0: none cached (or no device).  Reads the cache only
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    for (int i = 0; i < g_t9_cached; ++i)
+        if (g_t9_cache[i].device == device && g_t9_cache[i].h == h && g_t9_cache[i].w == w) return g_t9_cache[i].period;
+    return 0;
 }
 
 extern "C" int frhip_conv_wgrad(int dtype, const void* dy, const void* x, float* dw, int n, int h, int w, int c,

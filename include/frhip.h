@@ -63,6 +63,13 @@ int frhip_conv_stat_rows(int dtype, int m, int k, int h, int w, int c, int r, in
 /* test hook: 1 (default) = 3x3 / stride-1 bf16 weight gradients on the nine-tap kernel, 0 = on the per-tap gather kernel;
  * < 0 queries.  Returns the old value */
 int frhip_set_wgrad_taps9(int enabled);
+/* test hook: 1 (default) = a nine-tap weight gradient takes the lane-mask table of its map geometry when one can be had (at most 8
+ * geometries per process, period H W / gcd(H W, 64) <= 64, not inside a stream capture), 0 = it never asks and runs the twin that
+ * tracks the padding predicates per lane; < 0 queries.  Same sums either way.  Returns the old value */
+int frhip_set_wgrad_mask_table(int enabled);
+/* test hook: period (in K steps) of the lane-mask table cached for h x w maps on the current device, 0 if none is cached or no device
+ * is present.  Read-only: allocates nothing, launches nothing */
+int frhip_wgrad_mask_table_period(int h, int w);
 /* test hook: 0 disables the LDS-halo 3x3/s1 kernel (generic NT kernel is used instead), 1 automatic tile choice,
  * 2 forces the 4-wave 256x64 tile (two workgroups per CU), 3 the 8-wave 256x128 tile.  Returns the old value */
 int frhip_set_conv_halo(int enabled);
