@@ -12,7 +12,8 @@ Bounds are per element, never a fraction of the tensor maximum.  With u = 2^-24 
     reference (sqrt(K): the worst-case K u is vacuous at K = 100 352);
   * a partial sum over the rows of one 256-row tile costs 258 u * sum |term| (the worst case: the tiles are short);
   * an intermediate the kernel rounds to bf16 whose rounding may come out the other way than the reference's (it lies within the
-    kernel's fp32 error of a rounding boundary) costs one bf16 step of itself, carried through the products it enters.
+    kernel's fp32 error of a rounding boundary) costs one bf16 step of itself, carried through the products it enters;
+  * an attention probability below the smallest normal fp32 number (a key behind the -100 shift mask) may come out as 0: 2^-126, absolute.
 Each test's docstring states the bound it applies.  The negative controls at the end show that these bounds reject plausible defects."""
 import inspect
 import math
@@ -679,6 +680,11 @@ def attn_reference(qkv, dout, bias, scale, b, H, W, heads, ws, shift, use_mask=T
     dl = sc * dcos + 2.0 ** -20 * ((cos * sc).abs() + bb.abs() + 100.0 * masked)
     P = torch.softmax(logit, -1)
     dP = P * (torch.expm1(dl + dl.amax(-1, keepdim=True)) + 2.0 ** -18)            # logit errors + the fp32 exp / sum / divide
+    # fp32 underflow: a pair the shift mask separates in EVERY window of the map (maps one window wide or high) has P of order
+    # e^-100 = 3.7e-44, below the smallest normal fp32 number 2^-126; the kernel's exponential returns 0 for it (at most 2^-126 lost,
+    # the sum being >= 1), and the product P (dP - rd) may underflow the same way.  Relative terms cannot carry that: it is absolute.
+    FLUSH = 2.0 ** -126
+    dP = dP + FLUSH
     Pb = rb(P)
     tP = may_flip(P, dP) * (dP + ulp(P))                                            # the kernel's bf16 P may differ from Pb by this
     O = Pb @ v
@@ -705,7 +711,7 @@ def attn_reference(qkv, dout, bias, scale, b, H, W, heads, ws, shift, use_mask=T
     rd = (P * dPm).sum(-1, keepdim=True)
     drd = (dP * dPm.abs()).sum(-1, keepdim=True) + (P * ddP).sum(-1, keepdim=True) + 2.0 ** -19 * (P * dPm).abs().sum(-1, keepdim=True)
     dS = P * (dPm - rd)
-    ddS = dP * (dPm - rd).abs() + P * (ddP + drd) + 2.0 ** -22 * dS.abs()
+    ddS = dP * (dPm - rd).abs() + P * (ddP + drd) + 2.0 ** -22 * dS.abs() + FLUSH
     chunks, wpb = wm_chunks(nw, heads, _cus())
     nacc = wpb + chunks + 8
     res["dbias"] = (dS.sum(0), ddS.sum(0) + nacc * U32 * dS.abs().sum(0))

@@ -12,7 +12,11 @@ def partition(x, ws):
     return x.view(b, H // ws, ws, W // ws, ws).permute(0, 1, 3, 2, 4).reshape(-1, ws * ws)
 
 
-@pytest.mark.parametrize("geom", [(2, 12, 12, 6, 3), (3, 6, 6, 3, 1), (2, 14, 21, 7, 3), (2, 12, 12, 6, 0)])
+@pytest.mark.parametrize("geom", [(2, 12, 12, 6, 3), (3, 6, 6, 3, 1), (2, 14, 21, 7, 3), (2, 12, 12, 6, 0),
+                                  # one-token, 2 x 2, full-tile and two-tile windows; H != W both ways; H == ws (no slice 0 on that
+                                  # axis); the smallest and the largest shift
+                                  (2, 2, 3, 1, 0), (1, 4, 6, 2, 1), (2, 8, 8, 4, 3), (1, 4, 4, 4, 1), (1, 10, 15, 5, 4), (1, 15, 5, 5, 1),
+                                  (2, 5, 5, 5, 2), (1, 7, 7, 7, 3), (1, 7, 14, 7, 6), (1, 21, 7, 7, 1), (1, 12, 12, 6, 5), (1, 2, 2, 2, 1)])
 def test_window_index_is_the_rolled_partition_with_the_slice_mask(geom):
     b, H, W, ws, shift = geom
     pix, region = window_index(b, H, W, ws, shift, device="cpu")
