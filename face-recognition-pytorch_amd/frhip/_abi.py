@@ -18,7 +18,7 @@ class FrhipError(RuntimeError):
 
 def _ctype(decl):
     d = decl.strip()
-    if "*" in d:
+    if "*" in d or "[" in d:          # `int out[5]` is a pointer parameter
         return ctypes.c_void_p
     base = d.split()[0] if d.split() else d
     if d.startswith("frhip_stream_t"):

@@ -117,11 +117,19 @@ __global__ __launch_bounds__(256, 2) void halo_wide_kernel(HaloGeom g, const voi
 // frhip_set_epi_lean(0): always the general store epilogue (the lean kernels are bit-identical)
 int g_epi_lean = 1;
 
+// does a launch of this family (halo_family) run its LEAN instantiation?  The two 8-wave tiles have none.  Host only: the launchers
+// below and frhip_dgrad_route ask here
+bool halo_lean_pick(int family, long long M, int Nout, const EpiBnRed& br) {
+    if (family == HALO_WIDE) return g_epi_lean && epi_lean_ok(true, M, Nout, HaloWideTile::BM, HaloWideTile::BN, br);
+    typedef HaloTile<bf16_t, 4, 1, 4, 1> Tile;
+    return family == HALO_4WAVE && g_epi_lean && epi_lean_ok(true, M, Nout, Tile::BM, Tile::BN, br);
+}
+
 static int halo_wide_launch(const HaloGeom& g, const void* a, const void* b, void* out, const void* res, float* stats,
                             const EpiBnRed& br, hipStream_t stream) {
     typedef HaloWideTile Tile;
     const int mtiles = (g.M + Tile::BM - 1) / Tile::BM, ntiles = (g.Nout + Tile::BN - 1) / Tile::BN;
-    const bool lean = g_epi_lean && epi_lean_ok(true, g.M, g.Nout, Tile::BM, Tile::BN, br);
+    const bool lean = halo_lean_pick(HALO_WIDE, g.M, g.Nout, br);
     auto kern = lean ? halo_wide_kernel<true> : halo_wide_kernel<false>;
     if (set_dynamic_lds(reinterpret_cast<const void*>(kern), Tile::LDS, "igemm_halo")) return FRHIP_ELAUNCH;
     hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(Tile::THREADS), Tile::LDS, stream, g, a, b, out, res, stats, br, mtiles, ntiles);
@@ -137,7 +145,7 @@ static int halo_launch(const HaloGeom& g, const void* a, const void* b, void* ou
     // lean epilogue: the 4-wave bf16 tile (what the training step runs); the other configurations keep the general one
     constexpr bool HAS_LEAN = sizeof(T) == 2 && WM == 4 && WN == 1 && MT == 4 && HBUFS == 1;
     bool lean = false;
-    if constexpr (HAS_LEAN) lean = g_epi_lean && epi_lean_ok(true, g.M, g.Nout, Tile::BM, Tile::BN, br);
+    if constexpr (HAS_LEAN) lean = halo_lean_pick(HALO_4WAVE, g.M, g.Nout, br);
     auto kern = halo_kernel<T, WM, WN, MT, HBUFS, XF, false>;
     if constexpr (HAS_LEAN) { if (lean) kern = halo_kernel<T, WM, WN, MT, HBUFS, XF, true>; }
     if (set_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "igemm_halo")) return FRHIP_ELAUNCH;
@@ -189,6 +197,14 @@ static int halo_config(int dtype, int c, int k) {
     return narrow ? 1 : 2;
 }
 
+// the kernel halo_run launches for a problem without operand transform (c: gathered channels, k: output channels)
+int halo_family(int dtype, int w, int c, int k, int sign) {
+    if (halo_config_w(dtype, w, c, k, sign) == 3) return HALO_WIDE;
+    const int cfg = halo_config(dtype, c, k);
+    if (dtype == FRHIP_DT_BF16 && cfg == 0) return HALO_4WAVE;
+    return cfg == 1 ? HALO_8X1 : HALO_4X2;
+}
+
 // would halo_run take a LEAN kernel for this forward problem?  (frhip_conv_fwd_affine: the folded BatchNorm lives in the lean epilogue)
 bool halo_lean_applies(int dtype, int n, int h, int w, int c, int k, int sign) {
     if (!g_epi_lean || dtype != FRHIP_DT_BF16) return false;
@@ -223,12 +239,13 @@ int halo_run(int dtype, const void* a, const void* b, void* out, const void* res
         if (dtype != FRHIP_DT_BF16 || cfg != 0) { set_error("igemm_halo: operand transform not available for this shape"); return FRHIP_EINVAL; }
         return halo_launch<bf16_t, 4, 1, 4, 1, true>(g, a, b, out, res, stats, br, stream);
     }
-    if (halo_config_w(dtype, w, c, k, sign) == 3) return halo_wide_launch(g, a, b, out, res, stats, br, stream);
-    if (dtype == FRHIP_DT_BF16 && cfg == 0) return halo_launch<bf16_t, 4, 1, 4, 1>(g, a, b, out, res, stats, br, stream);   // bf16 only
+    const int family = halo_family(dtype, w, c, k, sign);
+    if (family == HALO_WIDE) return halo_wide_launch(g, a, b, out, res, stats, br, stream);
+    if (family == HALO_4WAVE) return halo_launch<bf16_t, 4, 1, 4, 1>(g, a, b, out, res, stats, br, stream);   // bf16 only
     return by_dtype(dtype, "igemm_halo", [&](auto t) {
         typedef decltype(t) T;
-        return cfg == 1 ? halo_launch<T, 8, 1, 2, 2>(g, a, b, out, res, stats, br, stream)
-                        : halo_launch<T, 4, 2, 4, 2>(g, a, b, out, res, stats, br, stream);
+        return family == HALO_8X1 ? halo_launch<T, 8, 1, 2, 2>(g, a, b, out, res, stats, br, stream)
+                                  : halo_launch<T, 4, 2, 4, 2>(g, a, b, out, res, stats, br, stream);
     });
 }
 

@@ -384,6 +384,10 @@ struct EpiOperands {
     }
 };
 
+// host side: the kernel family of a convolution launch, as frhip_dgrad_route reports it.  NT_GENERIC: the gather kernel of igemm_nt.hip;
+// the others: the halo kernels <4,1,4,1>, <8,1,2,2>, <4,2,4,2> and the 64 x 128-per-wave tile (igemm_halo.hip: halo_family)
+enum { NT_GENERIC = 0, HALO_4WAVE = 1, HALO_8X1 = 2, HALO_4X2 = 3, HALO_WIDE = 4 };
+
 // host side: may a launch use the LEAN kernels?  (bm x bn = the workgroup's tile)
 inline bool epi_lean_ok(bool bf16, long long M, int Nout, int bm, int bn, const EpiBnRed& br) {
     return bf16 && M % bm == 0 && Nout % bn == 0 && br.map.wc == 0 && br.res_w == 0 && !br.bias && !br.act && !br.gelu_bwd &&

@@ -10,6 +10,8 @@ bool halo_applicable(int dtype, int h, int w, int c, int k, int r, int s, int st
 int halo_stat_rows(int dtype, int m, int w, int c, int k, int sign);
 bool halo_xf_applicable(int dtype, int h, int w, int c, int k, int r, int s, int stride, int pad);
 bool halo_lean_applies(int dtype, int n, int h, int w, int c, int k, int sign);
+int halo_family(int dtype, int w, int c, int k, int sign);
+bool halo_lean_pick(int family, long long M, int Nout, const EpiBnRed& br);
 int halo_run(int dtype, const void* a, const void* b, void* out, const void* res, float* stats, const EpiBnRed& br,
              int n, int h, int w, int c, int k, int sign, hipStream_t stream, const float* xf_scale = nullptr,
              const float* xf_shift = nullptr, void* xf_out = nullptr);
@@ -136,6 +138,11 @@ static int nt_pick_tile(int dtype, const NtGeom& g) {
 
 static const EpiBnRed NO_BNRED = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, {0, 0, 0, 0, 0, 0}, nullptr, nullptr, 0};
 
+// does nt_dispatch run this launch on the persistent LEAN kernel of the 256 x 256 tile?  (`tile` from nt_pick_tile)
+static bool nt_takes_lean(int dtype, int tile, const NtGeom& g, const EpiBnRed& br, const float* stats, int splits, bool atomic) {
+    return dtype == FRHIP_DT_BF16 && tile == 4 && !atomic && splits == 1 && g_epi_lean && nt_lean_ok(true, g.M, g.Nout, br, stats);
+}
+
 static int nt_dispatch(int dtype, const NtGeom& g, const void* a, const void* b, void* out, const void* res,
                        float* stats, const EpiBnRed& br, int splits, bool atomic, hipStream_t stream) {
     const int tile = nt_pick_tile(dtype, g);
@@ -143,7 +150,7 @@ static int nt_dispatch(int dtype, const NtGeom& g, const void* a, const void* b,
     return atomic ? nt_launch_cfg<T, WM, WN, MT, EPI_ATOMIC>(g, a, b, out, res, stats, br, splits, stream)     \
                   : nt_launch_cfg<T, WM, WN, MT, EPI_STORE>(g, a, b, out, res, stats, br, splits, stream)
     if (dtype == FRHIP_DT_BF16 && (tile == 3 || tile == 4)) {     // the two tiles that fp32 lacks (nt_pick_tile never names them for fp32)
-        if (tile == 4 && !atomic && splits == 1 && g_epi_lean && nt_lean_ok(true, g.M, g.Nout, br, stats))
+        if (nt_takes_lean(dtype, tile, g, br, stats, splits, atomic))
             return nt_launch_cfg<bf16_t, 2, 4, 8, EPI_LEAN>(g, a, b, out, res, stats, br, splits, stream);
         if (tile == 4 && !atomic) return nt_launch_cfg<bf16_t, 2, 4, 8, EPI_STORE>(g, a, b, out, res, stats, br, splits, stream);
         NT_GO(bf16_t, 4, 2, 4);
@@ -320,6 +327,42 @@ extern "C" int frhip_dgrad_stat_rows(int dtype, int n, int h, int wd, int c, int
     }
     const int bm = nt_block_rows(dtype, g);
     return (m + bm - 1) / bm;
+}
+
+extern "C" int frhip_dgrad_route(int dtype, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad, int residual_stride,
+                                 int bnred, int out[5]) {
+    // what dgrad_run would launch for these arguments under the current switches, from the predicates it launches by; no device is touched
+    if (const int rc = by_dtype(dtype, "frhip_dgrad_route", [](auto) { return FRHIP_OK; })) return rc;
+    if (!out || residual_stride < 0 || residual_stride > 2) {
+        set_error("frhip_dgrad_route: out is required and residual_stride must be 0 (no residual), 1 or 2");
+        return FRHIP_EINVAL;
+    }
+    NtGeom g;
+    const int ho = (h + 2 * pad - r) / stride + 1, wo = (wd + 2 * pad - s) / stride + 1;
+    if (const int rc = fill_geom(g, dtype, n, ho, wo, k, h, wd, c, r, s, stride, pad, 1, "frhip_dgrad_route")) return rc;
+    // the predicates ask only WHETHER the epilogue has partial sums and a saved BatchNorm input: a host address stands for both
+    static const float present = 0.f;
+    const float* stats = bnred ? &present : nullptr;
+    EpiBnRed br = NO_BNRED;
+    br.y = stats;
+    if (residual_stride == 2) { br.res_h = h; br.res_w = wd; }
+    out[4] = frhip_dgrad_stat_rows(dtype, n, h, wd, c, k, r, s, stride, pad);
+    if (halo_applicable(dtype, h, wd, k, c, r, s, stride, pad)) {
+        out[0] = halo_family(dtype, wd, k, c, -1); out[1] = 0; out[2] = halo_lean_pick(out[0], g.M, g.Nout, br) ? 1 : 0; out[3] = 1;
+        return FRHIP_OK;
+    }
+    // one launch, or the non-empty parity classes; tile and epilogue of the first, -1 where a later class differs from it
+    out[0] = NT_GENERIC; out[1] = out[2] = out[3] = 0;
+    for (int cls = 0; cls < (dgrad_by_parity(g) ? 4 : 1); ++cls) {
+        NtGeom gc = g; EpiBnRed bc = br;
+        if (dgrad_by_parity(g) && parity_class(g, dtype, cls >> 1, cls & 1, gc, bc.map) == 0) continue;
+        const int tile = nt_pick_tile(dtype, gc);
+        const int epi = nt_takes_lean(dtype, tile, gc, bc, stats, 1, false) ? (bnred ? 2 : 1) : 0;
+        if (out[3]++ == 0) { out[1] = tile; out[2] = epi; }
+        if (out[1] != tile) out[1] = -1;
+        if (out[2] != epi) out[2] = -1;
+    }
+    return FRHIP_OK;
 }
 
 extern "C" int frhip_conv_dgrad_fused(int dtype, const void* dy, const void* wt, void* dx, const void* residual,

@@ -106,6 +106,19 @@ int frhip_conv_dgrad(int dtype, const void* dy, const void* wt, void* dx, const 
  * be NULL: no ReLU between the BN and this gradient) -- what frhip_bn_bwd_reduce would compute in a second pass over dx
  * and y_bn; feed it to frhip_bn_bwd_finalize. */
 int frhip_dgrad_stat_rows(int dtype, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad);
+/* Read-only query: the launches of a data-gradient, as frhip_conv_dgrad / _fused / _fused_rs / _bnred would run it with these arguments
+ * under the current frhip_set_conv_halo, frhip_set_halo_wide_dirs, frhip_set_nt_tile and frhip_set_epi_lean switches.  residual_stride: 0 no
+ * residual, 1 dense, 2 compact; bnred != 0: with BatchNorm-backward partials (y_bn given).  Same shape checks and errors as those entry
+ * points; touches no device.  out[5] (host memory):
+ *   [0] kernel family: 0 the generic gather kernel, 1 / 2 / 3 the halo tiles <4,1,4,1> / <8,1,2,2> / <4,2,4,2> (waves m, waves n, 16-pixel
+ *       blocks per wave, window buffers), 4 the 64 x 128-per-wave halo tile
+ *   [1] NT tile of the generic kernel as frhip_set_nt_tile numbers them (1 .. 4), 0 for a halo family
+ *   [2] store epilogue: 0 general, 1 lean, 2 lean in two 64-row halves (the 256 x 256 tile with BatchNorm-backward partials)
+ *   [3] launches: 1, or the non-empty parity classes of a 3x3 / stride-2 / pad-1 gradient (1 .. 4); [1] and [2] describe the first and are
+ *       -1 where a later class differs from it
+ *   [4] rows of stats_partial = frhip_dgrad_stat_rows(...) */
+int frhip_dgrad_route(int dtype, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad, int residual_stride, int bnred,
+                      int out[5]);
 int frhip_conv_dgrad_bnred(int dtype, const void* dy, const void* wt, void* dx, const void* residual,
                            const void* y_bn, const float* mean, const float* invstd, const float* mask_scale,
                            const float* mask_shift, float* stats_partial, int n, int h, int wd, int c, int k,
