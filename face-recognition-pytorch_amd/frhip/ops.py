@@ -855,6 +855,82 @@ def magface_norm_grad(norms, packed, rmax, rsum, s, eps, l_a, u_a, l_m, u_m, lam
     return dnorm
 
 
+ELASTIC_KINDS = {"arc": MARGIN_ARCFACE, "cos": MARGIN_COSFACE}
+
+
+def _elastic_args(who, n, std, seed, step):
+    _need_cuda(who, step=step)
+    if step.dtype != torch.int64 or step.numel() != 1:
+        raise ValueError("%s: step must be one int64 element, got %s %s" % (who, step.dtype, tuple(step.shape)))
+    if int(n) < 1 or not float(std) >= 0.0:
+        raise ValueError("%s: needs n >= 1 rows and std >= 0, got n=%r std=%r" % (who, n, std))
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF                      # the key is the seed's 64 bits; ctypes takes them as a signed value
+    return int(n), seed - (1 << 64) if seed >> 63 else seed
+
+
+def _elastic_kind(who, kind):
+    if kind not in ELASTIC_KINDS and kind not in ELASTIC_KINDS.values():
+        raise ValueError("%s: kind must be 'arc' (0) or 'cos' (1), got %r" % (who, kind))
+    return ELASTIC_KINDS.get(kind, kind)
+
+
+def elastic_margins(n, kind, mean, std, seed, step, update):
+    """ElasticFace's per-row margins in ONE launch (frhip_elastic_margins): row i's draw from N(mean, std) by Philox at (seed, step, i),
+    as m_ang (kind 'arc') or m_add (kind 'cos'), the other vector 0.  step: device scalar (int64); update: it is advanced by one in the
+    same launch, else every margin is float(mean) and step is only read.  No host sync.  -> (m_ang [n], m_add [n])"""
+    n, seed = _elastic_args("elastic_margins", n, std, seed, step)
+    kind = _elastic_kind("elastic_margins", kind)
+    out = torch.empty((2, n), dtype=torch.float32, device=step.device)
+    check(lib().frhip_elastic_margins(n, kind, mean, std, seed, _p(step), int(bool(update)), _p(out[0]), _p(out[1]), _s()),
+          "frhip_elastic_margins")
+    return out[0], out[1]
+
+
+def elastic_draws(n, mean, std, seed, step, update):
+    """the bare draws g [n] of elastic_margins (frhip_elastic_draws), for elastic_assign"""
+    n, seed = _elastic_args("elastic_draws", n, std, seed, step)
+    g = torch.empty((n,), dtype=torch.float32, device=step.device)
+    check(lib().frhip_elastic_draws(n, mean, std, seed, _p(step), int(bool(update)), _p(g), _s()), "frhip_elastic_draws")
+    return g
+
+
+def head_target_cos(ehat, what, labels_i32, subcenters=1):
+    """tcos [n] fp32: the cosine of every row with the centre of its label, the maximum over the class's sub-centres (what: subcenters x
+    classes rows, plane-major); exactly -2 where the label is -1 (frhip_head_target_cos)"""
+    _need_cuda("head_target_cos", ehat=ehat, what=what, labels=labels_i32)
+    k = _check_subcenters(what, subcenters)
+    n, d = ehat.shape
+    if (ehat.dtype not in _DT or what.dtype != ehat.dtype or what.shape[1] != d or labels_i32.dtype != torch.int32
+            or labels_i32.numel() != n or not (ehat.is_contiguous() and what.is_contiguous() and labels_i32.is_contiguous())):
+        raise ValueError("head_target_cos: ehat [n, d] and what [subcenters x classes, d] must be contiguous, of one dtype (bfloat16 or "
+                         "float32), labels int32 [n]; got %s %s, %s %s, %s %s" % (ehat.dtype, tuple(ehat.shape), what.dtype,
+                                                                                 tuple(what.shape), labels_i32.dtype, tuple(labels_i32.shape)))
+    tcos = torch.empty((n,), dtype=torch.float32, device=ehat.device)
+    check(lib().frhip_head_target_cos(dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, what.shape[0] // k, d, k, _p(tcos), _s()),
+          "frhip_head_target_cos")
+    return tcos
+
+
+def elastic_assign(tcos, g, kind):
+    """ElasticFace+: tcos [world_size, n] (or [n]) target cosines of all ranks, g [n] draws -> (m_ang [n], m_add [n]): the row with the
+    r-th largest cosine (maximum over ranks; ties in row order) gets the r-th smallest draw (frhip_elastic_assign; exact, n <= 65536)"""
+    _need_f32("elastic_assign", tcos=tcos, g=g)
+    kind = _elastic_kind("elastic_assign", kind)
+    n = g.numel()
+    tcos = tcos.reshape(1, -1) if tcos.dim() == 1 else tcos
+    if tcos.dim() != 2 or tcos.shape[1] != n or g.dim() != 1 or not (tcos.is_contiguous() and g.is_contiguous()):
+        raise ValueError("elastic_assign: tcos must be [world_size, %d] and g [%d], both contiguous, got %s, %s"
+                         % (n, n, tuple(tcos.shape), tuple(g.shape)))
+    nbytes = lib().frhip_elastic_assign_workspace(n)
+    if nbytes <= 0:
+        raise ValueError("elastic_assign: n = %d rows are not served (1 .. 65536)" % n)
+    work = torch.empty((nbytes // 4,), dtype=torch.int32, device=g.device)
+    out = torch.empty((2, n), dtype=torch.float32, device=g.device)
+    check(lib().frhip_elastic_assign(_p(tcos), tcos.shape[0], n, _p(g), kind, _p(out[0]), _p(out[1]), _p(work), nbytes, _s()),
+          "frhip_elastic_assign")
+    return out[0], out[1]
+
+
 def head_sub_max():
     """the largest number of sub-centres per class the head kernels serve"""
     return lib().frhip_head_sub_max()

@@ -10,6 +10,8 @@ autograd node.
 row's embedding before normalisation: `forward(logits, labels, norms)`.  It clamps EVERY cosine, so unlike the others it returns a new
 tensor and leaves `logits` untouched.  `MagFace(s, m, u_margin, l_a, u_a, lambda_g)` (Meng et al., CVPR 2021; not in the reference) does the
 same with a margin that grows with the norm; its regulariser and the gradient through the norms live in the fused head.
+`ElasticFace(s, m, std, kind, plus, seed)` (Boutros et al., CVPR-W 2022; not in the reference) draws every row's margin from N(m, std) at
+every step, and with `plus` hands the draws out by difficulty: `forward(logits, labels)`, a new tensor as well.
 
 Inside PartialFC the margin is not applied through this `forward`: it lives in the epilogue of the fused cos-theta
 MFMA kernel (frhip_head_fwd / frhip_head_fwd_ex), which only reads the module's constants through `margin_of`, so the
@@ -33,14 +35,20 @@ RowMargins = collections.namedtuple("RowMargins", "s eps m_ang m_add")
 # MagFace: the constants of the module (m, u_margin: the margin at norms l_a and u_a; lambda_g: the weight of the regulariser); the kernels
 # take RowMargins as well, filled by frhip_magface_margins
 MagMargin = collections.namedtuple("MagMargin", "s m u_margin l_a u_a lambda_g eps")
+# ElasticFace: the constants of the module (m, std: mean and deviation of the draws; kind "arc" / "cos"; plus: ranked assignment; seed:
+# the key of the generator); the kernels take RowMargins, filled by frhip_elastic_margins or frhip_elastic_draws + frhip_elastic_assign
+ElasticMargin = collections.namedtuple("ElasticMargin", "s m std kind plus seed eps")
 
-SUPPORTED = "ArcFace, CosFace, CombinedMarginLoss (ArcFace m1 == 1, m3 == 0 or CosFace m3 > 0), AdaFace, MagFace"
+SUPPORTED = "ArcFace, CosFace, CombinedMarginLoss (ArcFace m1 == 1, m3 == 0 or CosFace m3 > 0), AdaFace, MagFace, ElasticFace"
 
 
 def margin_of(module):
     """-> Margin of a margin module of this package, read from its attributes NOW (so a later `easy_margin = True` counts, as in
-    the reference, whose modules read their attributes in forward); AdaMargin for AdaFace, MagMargin for MagFace.  NotImplementedError
-    for any other module."""
+    the reference, whose modules read their attributes in forward); AdaMargin for AdaFace, MagMargin for MagFace, ElasticMargin for
+    ElasticFace.  NotImplementedError for any other module."""
+    if isinstance(module, ElasticFace):
+        return ElasticMargin(float(module.s), float(module.m), float(module.std), module.kind, bool(module.plus), int(module.seed),
+                             float(module.eps))
     if isinstance(module, AdaFace):
         return AdaMargin(float(module.s), float(module.m), float(module.h), float(module.t_alpha), float(module.eps))
     if isinstance(module, MagFace):
@@ -238,3 +246,83 @@ class MagFace(torch.nn.Module):
 def _hip_magface_margins(norms, mg):
     from frhip import ops
     return ops.magface_margins(norms.float(), mg.l_a, mg.u_a, mg.m, mg.u_margin)
+
+
+class ElasticFace(torch.nn.Module):
+    """Elastic margin (ElasticFace, Boutros et al., CVPR-W 2022): at every training step row i of the GLOBAL batch draws g_i from N(m, std);
+    kind "arc": target logit s cos(clip(theta + g_i, eps, pi - eps)), kind "cos": s (cos(clip(theta, eps, pi - eps)) - g_i); every cosine
+    is clamped to [-1 + eps, 1 - eps] first and every logit is x s (the per-row margin kernels' rule: the clip of the angle at pi - eps
+    stands where the official code has none).  The published presets (m, std): Arc (0.5, 0.05), Cos (0.35, 0.05), Arc+ (0.5, 0.0175),
+    Cos+ (0.35, 0.025).
+
+    Draws: Philox4x32-10 keyed by `seed`, counter (row, step), Box-Muller in float64 (include/frhip.h, frhip_elastic_margins): a draw
+    depends on (seed, step, row) alone, so every rank derives the whole batch's margins with no collective.  `step` is a device buffer
+    (int64, checkpointed), advanced by the kernel itself in training mode; in eval mode every margin is m and `step` stands still.
+
+    plus=True (ElasticFace-Arc+ / -Cos+): the draws are handed out by difficulty.  With c_i the row's target cosine (the maximum over
+    sub-centres and over the ranks' shards, -2 where nobody owns the row) and r_i = #{j : c_j > c_i, or c_j == c_i and j < i}, row i gets
+    the r_i-th smallest draw: the largest cosine gets the smallest margin.  This is the paper's stated rule; the official code indexes
+    the sorted margins with the sort permutation itself instead of the rank.  No gradient flows through the ranking or the margins."""
+    eps = 1e-3
+    KINDS = ("arc", "cos")
+
+    def __init__(self, s=64.0, m=0.5, std=0.05, kind="arc", plus=False, seed=0):
+        super().__init__()
+        if kind not in self.KINDS:
+            raise ValueError("ElasticFace: kind must be 'arc' or 'cos', got %r" % (kind,))
+        if not std >= 0:
+            raise ValueError("ElasticFace: std must be >= 0, got %r" % (std,))
+        self.s, self.m, self.std, self.kind, self.plus, self.seed = s, m, std, kind, bool(plus), int(seed)
+        self.scale, self.margin = s, m
+        self.register_buffer("step", torch.zeros(1, dtype=torch.int64))
+
+    def row_margins(self, kernels=None, tcos=None, n=None):
+        """-> RowMargins of the n rows of the global batch; in training mode `step` is advanced.  tcos ([world_size, n] or [n], detached):
+        the target cosines `plus` ranks by, required in training mode with plus (n is then read off it); eval mode never looks at it.
+        ONE launch without plus, three with it; no host synchronisation.  kernels: PartialFC's kernel object (tests swap in a double)."""
+        mg = margin_of(self)
+        kern = kernels if kernels is not None else _HipElastic
+        ranked = mg.plus and self.training
+        if ranked:
+            if tcos is None:
+                raise ValueError("ElasticFace(plus=True) ranks the draws by the rows' target cosines: pass tcos")
+            tcos = tcos.detach()
+            tcos = tcos.reshape(1, -1) if tcos.dim() == 1 else tcos
+            n = tcos.shape[1]
+        elif n is None:
+            if tcos is None:
+                raise ValueError("ElasticFace.row_margins: the number of rows n is needed")
+            n = tcos.shape[-1]
+        if ranked:
+            m_ang, m_add = kern.elastic_assign(tcos, kern.elastic_margins(n, mg, self.step, True, bare=True), mg)
+        else:
+            m_ang, m_add = kern.elastic_margins(n, mg, self.step, self.training)
+        return RowMargins(mg.s, mg.eps, m_ang, m_add)
+
+    def forward(self, logits: torch.Tensor, labels: torch.Tensor):
+        """The margin on explicit cosines [N, C] (labels [N] or [N, 1], -1 = no target): -> the scaled logits, a new tensor like
+        AdaFace.forward, differentiable in `logits`.  With plus the target cosines are read off `logits`."""
+        lab = labels.reshape(-1).long()
+        tcos = None
+        if self.plus and self.training:
+            picked = logits.detach().float().gather(1, lab.clamp(min=0).view(-1, 1)).view(-1)
+            tcos = torch.where(lab >= 0, picked, torch.full_like(picked, -2.0)).contiguous()
+        if self.step.device != logits.device:
+            raise RuntimeError("nets.ArcFace (frhip): ElasticFace's step buffer must live on the logits' device: module.to(device)")
+        return _RowMarginFn.apply(logits, labels, self.row_margins(None, tcos, n=logits.shape[0]))
+
+
+class _HipElastic:
+    """ElasticFace's launches for the stand-alone module: the three methods nets.PartialFC.HipHeadKernels has under the same names"""
+
+    @staticmethod
+    def elastic_margins(n, mg, step, update, bare=False):
+        from frhip import ops
+        if bare:
+            return ops.elastic_draws(n, mg.m, mg.std, mg.seed, step, update)
+        return ops.elastic_margins(n, mg.kind, mg.m, mg.std, mg.seed, step, update)
+
+    @staticmethod
+    def elastic_assign(tcos, g, mg):
+        from frhip import ops
+        return ops.elastic_assign(tcos.float().contiguous(), g, mg.kind)

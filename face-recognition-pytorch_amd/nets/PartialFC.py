@@ -22,7 +22,9 @@ What runs where
     :510-519).  AdaFace alone adds a fifth, small one: an all-gather of the rows' norms ([N] floats), from which every rank derives the
     same per-row margins and the same running statistics (frhip_adaface_margins, one launch).  MagFace gathers the norms the same way
     (frhip_magface_margins: margins and regulariser in one launch) and returns d loss / d norm of its own rows from the statistics every
-    rank already holds (frhip_magface_norm_grad), with no further collective.
+    rank already holds (frhip_magface_norm_grad), with no further collective.  ElasticFace draws its per-row margins on every rank from
+    (seed, step, row) with no collective at all (frhip_elastic_margins); its "+" variants add one all-gather of the rows' target cosines
+    ([N] floats per rank, frhip_head_target_cos), which every rank merges and ranks itself (frhip_elastic_assign).
 `conf.subcenters = K` (not in the reference; sub-center ArcFace): every class owns K centres, the table is plane-major [K x num_local, D]
 (centre k of class c in row k * num_local + c), the fused kernels take the maximum over a class's centres on their accumulators and send
 its gradient to the winner alone; sampling, sharding and the collectives stay at class level.  Absent or 1: the calls made before.
@@ -36,8 +38,8 @@ from typing import Callable
 import torch
 from torch import distributed
 
-from .ArcFace import (SUPPORTED as SUPPORTED_MARGINS, AdaFace, AdaMargin, ArcFace, CombinedMarginLoss, CosFace, MagFace, MagMargin,
-                      RowMargins, is_plain_arcface, margin_of)
+from .ArcFace import (SUPPORTED as SUPPORTED_MARGINS, AdaFace, AdaMargin, ArcFace, CombinedMarginLoss, CosFace, ElasticFace, ElasticMargin,
+                      MagFace, MagMargin, RowMargins, is_plain_arcface, margin_of)
 
 
 import os
@@ -75,6 +77,21 @@ class HipHeadKernels:
         """-> d loss / d norms [N] x out_scale; packed [ws, N, 3]: the pack_stats blocks of all ranks, rmax / rsum: the global statistics"""
         return self.ops.magface_norm_grad(norms.float(), packed, rmax, rsum, mg.s, mg.eps, mg.l_a, mg.u_a, mg.m, mg.u_margin, mg.lambda_g,
                                           gscale, upstream, out_scale)
+
+    def elastic_margins(self, n, mg, step, update, bare=False):
+        """-> (m_ang, m_add) [n]: ElasticFace's draws at (mg.seed, step, row); update: step is advanced in the same launch, else every
+        margin is mg.m.  bare: the draws g [n] themselves, for elastic_assign.  mg: nets.ArcFace.ElasticMargin"""
+        if bare:
+            return self.ops.elastic_draws(n, mg.m, mg.std, mg.seed, step, update)
+        return self.ops.elastic_margins(n, mg.kind, mg.m, mg.std, mg.seed, step, update)
+
+    def head_target_cos(self, ehat, what, labels_i32, subcenters=1):
+        """-> tcos [n] fp32: every row's cosine with the centre of its label (the maximum over sub-centres), -2 where the label is -1"""
+        return self.ops.head_target_cos(ehat, what, labels_i32, subcenters)
+
+    def elastic_assign(self, tcos, g, mg):
+        """tcos [ws, n] of all ranks, g [n] -> (m_ang, m_add): the r-th largest cosine gets the r-th smallest draw"""
+        return self.ops.elastic_assign(tcos, g, mg.kind)
 
     def rescale(self, rowsum, local_max, global_max):
         self.ops.head_rescale(rowsum, local_max, global_max)
@@ -189,14 +206,17 @@ class _MarginSoftmaxFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, local_embeddings, weight_activated, labels_i32, kern, s, m, world_size, collectives, margin=None, adaface=None,
-                subcenters=1, sub_out=None, magface=None, local_norms=None):
+                subcenters=1, sub_out=None, magface=None, local_norms=None, elastic=None):
         """adaface: None, or (AdaFace module, this rank's norms [rows]) -- the per-row margins are then derived here, from the norms of
         the global batch in rank order, and `margin` is ignored.
         subcenters = K > 1: weight_activated holds K x classes rows, plane-major; the winning centre of every row's target (int32 [N], -1
         where another shard owns the row) is appended to the list sub_out
         magface: None, or the MagFace module, with local_norms = this rank's norms [rows] as a tensor input of the node: margins and
         regulariser are derived here from the gathered norms, the loss is CE + lambda_g reg, and backward returns the gradient of this
-        rank's norms when they require one"""
+        rank's norms when they require one
+        elastic: None, or the ElasticFace module: the per-row margins are drawn here (every rank draws the whole global batch's); with
+        `plus` in training mode the rows' target cosines are computed from the normalised operands, all-gathered ([rows] floats per rank)
+        and ranked first.  `margin` is ignored"""
         local_embeddings = local_embeddings.contiguous()
         rows, dim = local_embeddings.shape
         if collectives:                                                         # :182 (C1)
@@ -221,6 +241,15 @@ class _MarginSoftmaxFn(torch.autograd.Function):
             own = local_norms.detach().reshape(-1).contiguous()
             norms = _all_gather_flat(own.new_empty(world_size * rows), own) if collectives else own
             rm, reg = magface.row_margins(norms, kern)      # ONE launch: both margin vectors and the regulariser
+            extra, row_vecs = {"margin": rm}, (rm.m_ang, rm.m_add)
+            ctx.row_consts = (rm.s, rm.eps)
+        if elastic is not None:
+            tcos = None
+            if elastic.plus and elastic.training:
+                mine = kern.head_target_cos(ehat, what, labels_i32, subcenters)
+                tcos = _all_gather_flat(mine.new_empty(world_size * mine.numel()), mine) if collectives else mine
+                tcos = tcos.view(-1, mine.numel())
+            rm = elastic.row_margins(kern, tcos, n=ehat.shape[0])
             extra, row_vecs = {"margin": rm}, (rm.m_ang, rm.m_add)
             ctx.row_consts = (rm.s, rm.eps)
         if subcenters > 1:                                   # one centre per class: the calls made before sub-centres existed
@@ -258,7 +287,7 @@ class _MarginSoftmaxFn(torch.autograd.Function):
         up = grad_loss.reshape(1).float().contiguous()
         if not ctx.collectives:
             d_e, d_w = ctx.kern.backward(ehat, enorm, what, wnorm, labels_i32, ctx.s, ctx.m, rmax, rsum, ehat.shape[0], up, **extra)
-            return (d_e, d_w) + (None,) * 11 + (_MarginSoftmaxFn._norm_grad(ctx, rmax, rsum, up, 0, 1.0),)
+            return (d_e, d_w) + (None,) * 11 + (_MarginSoftmaxFn._norm_grad(ctx, rmax, rsum, up, 0, 1.0), None)
         # :504-522 (C6): reduce-scatter(SUM) of dE, x world_size (folded into the normalise-backward's scale); issued as soon
         # as dE is enqueued so that it runs beside the dW GEMM
         pending = []
@@ -272,7 +301,7 @@ class _MarginSoftmaxFn(torch.autograd.Function):
         d_local, work = pending[0]
         if work is not None:
             work.wait()
-        return (d_local, d_w) + (None,) * 11 + (_MarginSoftmaxFn._norm_grad(ctx, rmax, rsum, up, rank, float(ctx.world_size)),)
+        return (d_local, d_w) + (None,) * 11 + (_MarginSoftmaxFn._norm_grad(ctx, rmax, rsum, up, rank, float(ctx.world_size)), None)
 
     @staticmethod
     def _norm_grad(ctx, rmax, rsum, up, rank, scale):
@@ -368,7 +397,7 @@ class _PartialFCBase(torch.nn.Module):
             self.margin_softmax = margin_loss(conf.loss_s, conf.loss_m)
         else:
             raise
-        if not isinstance(self.margin_softmax, (ArcFace, CosFace, CombinedMarginLoss, AdaFace, MagFace)):
+        if not isinstance(self.margin_softmax, (ArcFace, CosFace, CombinedMarginLoss, AdaFace, MagFace, ElasticFace)):
             raise NotImplementedError("the fused head kernel implements the margin modules %s, not %s"
                                       % (SUPPORTED_MARGINS, type(self.margin_softmax).__name__))
         self._kernels = kernels
@@ -622,6 +651,8 @@ class _PartialFCBase(torch.nn.Module):
         tail = (None, (self.margin_softmax, norms)) if isinstance(mg, AdaMargin) else (margin,)
         if isinstance(mg, MagMargin):                            # the norms are a tensor input of the node: it returns their gradient
             tail = (None, None, 1, None, self.margin_softmax, norms)
+        if isinstance(mg, ElasticMargin):                        # the margins are drawn inside the node, from the module's step counter
+            tail = (None, None, 1, None, None, None, self.margin_softmax)
         if ready is not None and ready.numel() == n_global:      # everything label-side was done by prepare()
             return self._margin_softmax(local_embeddings, ready, s, m, collectives, tail)
         n_pos = None
@@ -731,6 +762,10 @@ class _PartialFCBase(torch.nn.Module):
                 buf, src = getattr(self.margin_softmax, name), state_dict.get("margin_softmax." + name)
                 with torch.no_grad():
                     buf.copy_(src.to(buf.device).reshape(buf.shape)) if src is not None else buf.fill_(init)
+        if isinstance(self.margin_softmax, ElasticFace):          # the step counter of the draws; a checkpoint without it starts at 0
+            buf, src = self.margin_softmax.step, state_dict.get("margin_softmax.step")
+            with torch.no_grad():
+                buf.copy_(src.to(buf.device).reshape(buf.shape)) if src is not None else buf.zero_()
         rows = self.subcenters * self.num_local
         if state_dict["weight"].dim() != 2 or state_dict["weight"].shape[0] != rows:
             raise ValueError("load_state_dict: this head holds %d sub-centre(s) x %d classes = %d rows (plane-major: row k * %d + c), "

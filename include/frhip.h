@@ -425,6 +425,39 @@ int frhip_head_bwd_dt_sub_rows(int dtype, const void* ehat, const void* what, co
                                float gscale, const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt,
                                frhip_stream_t stream);
 
+/* ElasticFace (not in the reference: Boutros et al., CVPR-W 2022): row i's margin is a draw g_i from N(mean, std), new at every step;
+ * kind 0 (FRHIP_MARGIN_ARCFACE): m_ang[i] = g_i, m_add[i] = 0; kind 1 (FRHIP_MARGIN_COSFACE): m_ang[i] = 0, m_add[i] = g_i.  The head
+ * then applies the per-row rule of frhip_margin_rows_t above (its clip of the angle at pi - eps stands where the official code has none).
+ * Draws: Philox4x32-10, key = (seed low 32 bits, seed high 32 bits), counter = (i, 0, step low 32, step high 32); one round is
+ *   p0 = 0xD2511F53 c0, p1 = 0xCD9E8D57 c2 (64-bit products); c <- (hi(p1) ^ c1 ^ k0, lo(p1), hi(p0) ^ c3 ^ k1, lo(p0));
+ *   k0 += 0x9E3779B9, k1 += 0xBB67AE85.
+ * With outputs x0 .. x3, in float64: u1 = (x0 + 0.5) 2^-32, u2 = (x1 + 0.5) 2^-32, z = sqrt(-2 ln u1) cos(2 pi u2),
+ * g_i = float(mean + std z); x2, x3 are unused.  A draw depends on (seed, step, i) alone -- not on n, and not on who computes it: every
+ * rank derives the draws of the whole global batch without a collective.
+ * step: device scalar (int64).  update != 0 (training): read, used, and step + 1 written back by the same launch (ONE workgroup, no host
+ * synchronisation, capturable); update == 0 (eval): every g_i = float(mean) and step is only read.
+ * frhip_elastic_draws writes the bare draws g[n] (for frhip_elastic_assign).
+ * n < 1, a null pointer, std < 0 or a kind outside {0, 1}: FRHIP_EINVAL, nothing is launched. */
+int frhip_elastic_margins(int n, int kind, double mean, double std, long long seed, long long* step, int update, float* m_ang,
+                          float* m_add, frhip_stream_t stream);
+int frhip_elastic_draws(int n, double mean, double std, long long seed, long long* step, int update, float* g, frhip_stream_t stream);
+/* The target cosine of every row on the shard that owns it (the key ElasticFace+ ranks by): tcos[i] = max over the class's `subcenters`
+ * centres (plane-major, as in frhip_head_fwd_sub) of the fp32 dot of ehat[i] with what[k * classes + labels[i]]; exactly -2.0f where
+ * labels[i] is -1.  One wavefront per row, 16-byte loads, the sum in an order fixed by d; no atomics.  dtype, d: those of frhip_head_fwd.
+ * Bad shape / dtype, subcenters outside 1 .. frhip_head_sub_max() or a null pointer: FRHIP_EINVAL, nothing is launched. */
+int frhip_head_target_cos(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d, int subcenters,
+                          float* tcos, frhip_stream_t stream);
+/* ElasticFace+: hand the draws out by difficulty.  tcos [world_size][n]: the frhip_head_target_cos vectors of all ranks (world_size 1:
+ * this rank's own); c_i = max over ranks (-2 where no rank owns the row; a NaN counts as -2).  rank r_i = #{j : c_j > c_i, or c_j == c_i
+ * and j < i}; with the draws sorted ascending, g_(0) <= ... <= g_(n-1) (equal draws in index order), row i gets g_(r_i): the largest
+ * cosine gets the smallest margin, unowned rows rank last.  m_ang / m_add by kind as above.  Exact and deterministic (counting ranks, no
+ * atomics) for 1 <= n <= 65536.  g must hold no NaN and must not overlap m_ang / m_add.
+ * work: caller-owned device scratch of frhip_elastic_assign_workspace(n) bytes (0 for an n that is not served), 4-byte aligned.
+ * Two launches.  Bad arguments or a workspace too small: FRHIP_EINVAL, nothing is launched. */
+int frhip_elastic_assign_workspace(int n);
+int frhip_elastic_assign(const float* tcos, int world_size, int n, const float* g, int kind, float* m_ang, float* m_add, void* work,
+                         size_t work_bytes, frhip_stream_t stream);
+
 /* ---- bn1 -> relu -> conv2 of a BasicBlock (nets/resnet.py:91-93) WITHOUT the activated tensor: the BatchNorm-apply + ReLU
  * is folded into the operand path of the convolution (forward) and of its weight gradient, which read the saved BatchNorm
  * INPUT x and form relu(x * in_scale[c] + in_shift[c]) in LDS.  bf16, 3x3 / stride 1 / pad 1; *_fusable() tells whether a
