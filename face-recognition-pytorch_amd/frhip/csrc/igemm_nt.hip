@@ -280,6 +280,44 @@ extern "C" int frhip_conv_fwd_bnrelu(int dtype, const void* x, const float* in_s
     return halo_run(dtype, x, w, y, nullptr, stats_partial, NO_BNRED, n, h, wd, c, k, +1, stream, in_scale, in_shift, act_out);
 }
 
+extern "C" int frhip_conv_fwd_route(int dtype, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad, int mode, int out[5]) {
+    // what frhip_conv_fwd (mode 0), frhip_conv_fwd_affine (1) or frhip_conv_fwd_bnrelu (2) would launch for these arguments under the
+    // current switches, from the predicates they launch by; no device is touched
+    if (const int rc = by_dtype(dtype, "frhip_conv_fwd_route", [](auto) { return FRHIP_OK; })) return rc;
+    if (!out || mode < 0 || mode > 2) {
+        set_error("frhip_conv_fwd_route: out is required and mode must be 0 (frhip_conv_fwd), 1 (_affine) or 2 (_bnrelu)");
+        return FRHIP_EINVAL;
+    }
+    NtGeom g;
+    const int ho = (h + 2 * pad - r) / stride + 1, wo = (wd + 2 * pad - s) / stride + 1;
+    if (const int rc = fill_geom(g, dtype, n, h, wd, c, ho, wo, k, r, s, stride, pad, 0, "frhip_conv_fwd_route")) return rc;
+    if (mode == 2 && !halo_xf_applicable(dtype, h, wd, c, k, r, s, stride, pad)) {
+        set_error("frhip_conv_fwd_route: frhip_conv_fwd_bnrelu is not fusable for this shape");
+        return FRHIP_EINVAL;
+    }
+    const bool halo = halo_applicable(dtype, h, wd, c, k, r, s, stride, pad);
+    // the predicates ask only WHETHER the epilogue folds a BatchNorm: a host address stands for scale and shift
+    static const float present = 0.f;
+    EpiBnRed br = NO_BNRED;
+    out[1] = 0; out[3] = 1;
+    out[4] = frhip_conv_stat_rows(dtype, g.M, k, h, wd, c, r, s, stride, pad);
+    if (mode == 2) {                                               // halo_run: the operand transform lives in the 4-wave tile alone
+        out[0] = HALO_4WAVE; out[2] = halo_lean_pick(HALO_4WAVE, g.M, g.Nout, br) ? 1 : 0;
+        return FRHIP_OK;
+    }
+    if (mode == 1) {
+        if (halo && halo_lean_applies(dtype, n, h, wd, c, k, +1)) br.aff_scale = br.aff_shift = &present;
+        else out[3] = 2;                                           // frhip_conv_fwd as below, then frhip_bn_apply in place
+    }
+    if (halo) {
+        out[0] = halo_family(dtype, wd, c, k, +1); out[2] = halo_lean_pick(out[0], g.M, g.Nout, br) ? 1 : 0;
+        return FRHIP_OK;
+    }
+    out[0] = NT_GENERIC; out[1] = nt_pick_tile(dtype, g);
+    out[2] = nt_takes_lean(dtype, out[1], g, br, nullptr, 1, false) ? 1 : 0;
+    return FRHIP_OK;
+}
+
 static int dgrad_run(int dtype, const void* dy, const void* wt, void* dx, const void* residual, float* stats,
                      const EpiBnRed& br, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad,
                      hipStream_t stream, const char* who) {

@@ -96,6 +96,15 @@ int frhip_conv_fwd_affine(int dtype, const void* x, const void* w, void* y, cons
                           frhip_stream_t stream);
 int frhip_conv_fwd(int dtype, const void* x, const void* w, void* y, float* stats_partial,
                    int n, int h, int wd, int c, int k, int r, int s, int stride, int pad, frhip_stream_t stream);
+/* Read-only query: the launches of a forward convolution, as frhip_conv_fwd (mode 0), frhip_conv_fwd_affine (mode 1) or
+ * frhip_conv_fwd_bnrelu (mode 2) would run it with these arguments under the current frhip_set_conv_halo, frhip_set_halo_wide_dirs,
+ * frhip_set_nt_tile and frhip_set_epi_lean switches.  Same shape checks and errors as those entry points (mode 2 on a shape that
+ * frhip_conv_bnrelu_fusable refuses: FRHIP_EINVAL); touches no device.  out[5] (host memory):
+ *   [0] kernel family and [1] NT tile, as frhip_dgrad_route numbers them
+ *   [2] store epilogue: 0 general, 1 lean (the folded BatchNorm of mode 1 exists in the lean epilogue only)
+ *   [3] launches: 1, or 2 where frhip_conv_fwd_affine runs the convolution ([0] .. [2] describe it) and then frhip_bn_apply in place
+ *   [4] rows of stats_partial = frhip_conv_stat_rows(...) */
+int frhip_conv_fwd_route(int dtype, int n, int h, int wd, int c, int k, int r, int s, int stride, int pad, int mode, int out[5]);
 /* dx[n,h,w,c] = conv_transpose(dy[n,ho,wo,k], w) (+ residual[n,h,w,c] if not NULL); wt = frhip_pack_wt(w) = [c][r][s][k].
  * autograd of nn.Conv2d w.r.t. input; the residual add is the gradient fan-in of `out += residual` (nets/resnet.py:101). */
 int frhip_conv_dgrad(int dtype, const void* dy, const void* wt, void* dx, const void* residual,

@@ -53,6 +53,8 @@ def test_unknown_dtype_is_refused_first_in_one_wording():
     names.append("frhip_wgrad_plan")            # no stream: a read-only query, behind the same guard as the weight gradients it plans
     names.append("frhip_dgrad_route")           # likewise for the data-gradients; its `int out[5]` binds as a pointer
     assert protos["frhip_dgrad_route"][1][-1] is ctypes.c_void_p and len(protos["frhip_dgrad_route"][1]) == 13
+    names.append("frhip_conv_fwd_route")        # and for the forward convolutions
+    assert protos["frhip_conv_fwd_route"][1][-1] is ctypes.c_void_p and len(protos["frhip_conv_fwd_route"][1]) == 12
     for name in names:
         args = [2] + [None if t is ctypes.c_void_p else t(0) for t in protos[name][1][1:]]
         rc = getattr(lib, name)(*args)
