@@ -11,6 +11,8 @@
 // :94-106 CosFace) are compile-time variants of the same epilogue (template arguments MK, FILT of head_epilogue), and so is the per-row
 // margin (MG_ROWS: AdaFace and MagFace, not in the reference), whose two margins per row come from adaface_margins_kernel or
 // magface_margins_kernel below; MagFace's gradient through the norms is magface_norm_grad_kernel and l2norm_bwd_norm*_kernel.
+// CurricularFace (MG_CURR, not in the reference) is the one variant that also changes the non-target elements by a per-row test; its
+// thresholds come from curricular_rows_kernel (curricular.hip).
 #include "igemm_nt.h"
 #include "margin_shared.h"
 #include "frhip.h"
@@ -23,11 +25,13 @@ struct MarginConstEx : MarginConst { float m3, thr; };       // CosFace margin, 
 // argument, so its kernel-argument layout and code are exactly those it had before the variants existed.
 // (named constants and a traits struct, not an unnamed enum in std::conditional: the kernels' mangled names must come out the same in the
 // host and the device compilation, and an unnamed type is numbered differently in the two)
-constexpr int MG_ARC = 0, MG_ARC_EASY = 1, MG_COS = 2, MG_ROWS = 3;
+constexpr int MG_ARC = 0, MG_ARC_EASY = 1, MG_COS = 2, MG_ROWS = 3, MG_CURR = 4;
 struct MarginRows { float s, eps; const float* m_ang; const float* m_add; };      // per-row margins: [M] angular, [M] additive
+struct MarginCurr : MarginConst { const float* thr; const float* t; };            // CurricularFace: [M] thresholds, the device scalar t
 template <int MK, bool FILT> struct MarginArgOf { typedef MarginConstEx type; };
 template <> struct MarginArgOf<MG_ARC, false> { typedef MarginConst type; };
 template <> struct MarginArgOf<MG_ROWS, false> { typedef MarginRows type; };
+template <> struct MarginArgOf<MG_CURR, false> { typedef MarginCurr type; };
 template <int MK, bool FILT>
 using MarginArg = typename MarginArgOf<MK, FILT>::type;
 
@@ -168,7 +172,8 @@ __global__ __launch_bounds__(256) void l2norm_bwd_norm_kernel(const float* __res
 // FWD = false: acc becomes d(loss)/d(cos), from the recomputed cosines and the global row max / sum; 0 in rows past M and classes past Nout.
 // MK: MG_ARC (cos(theta + m), below cos(pi - m) t - m sin(pi - m)), MG_ARC_EASY (cos(theta + m) for t > 0, else t), MG_COS (t - m3),
 // MG_ROWS (row m: every cosine clamped to [-1 + eps, 1 - eps], target cos(clamp(theta + m_ang[m], eps, pi - eps)) - m_add[m], slope 0 where
-// a clamp binds; frhip_margin_rows_t in frhip.h).
+// a clamp binds; frhip_margin_rows_t in frhip.h), MG_CURR (the target as MG_ARC; a non-target of row m whose clamped cosine is > thr[m]
+// becomes t (tt + t), slope tt + 2 t, tt = *mc.t read once per wave; a label -1 row has no exempt column; frhip_margin_curr_t in frhip.h).
 // FILT: interclass filtering (reference nets/ArcFace.py:28-39): an element that is not its row's target and whose clamped cosine is
 // > thr is multiplied by 0 -- logit 0, which still counts in the softmax sum, and d/dcos 0 (the reference builds the mask under
 // no_grad); a row without a target on this shard (label -1) is filtered in every column.
@@ -183,6 +188,8 @@ __device__ __forceinline__ void head_epilogue(int lane, const NtGeom& g, f32x4_t
                                               const float* upstream) {
     const int fi = lane & 15, fg = lane >> 4;
     if (!FWD && upstream) gscale *= upstream[0];        // d(loss)/d(loss) stays on the device: no host sync
+    [[maybe_unused]] float curr_t = 0.f, curr_thr = 2.f;                      // MG_CURR only
+    if constexpr (MK == MG_CURR) curr_t = mc.t[0];
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
         const int m = m0 + mt * 16 + fi;
@@ -195,6 +202,7 @@ __device__ __forceinline__ void head_epilogue(int lane, const NtGeom& g, f32x4_t
             tlo = -1.f + mc.eps; thi = 1.f - mc.eps;
             if (lab >= 0) { m_ang = mc.m_ang[m]; m_add = mc.m_add[m]; }       // lab >= 0 implies m < M
         }
+        if constexpr (MK == MG_CURR) curr_thr = mrow ? mc.thr[m] : 2.f;       // every row of the batch has one, label -1 rows too
         if constexpr (SUB)
             if (FWD && group == 0 && fg == 0 && mrow && lab < 0) tsub[m] = -1;
         float z[4][4];
@@ -220,11 +228,15 @@ __device__ __forceinline__ void head_epilogue(int lane, const NtGeom& g, f32x4_t
                         if (t > 0.f) { slope = mc.cos_m + t * mc.sin_m / sin_t; t = t * mc.cos_m - sin_t * mc.sin_m; }
                     } else if constexpr (MK == MG_ROWS) {
                         t = rows_margin_target(t, m_ang, m_add, mc.eps, slope);
+                    } else if constexpr (MK == MG_CURR) {
+                        t = curr_target(t, mc, slope);
                     } else {
                         t = t - mc.m3;
                     }
                 } else if constexpr (FILT) {
                     if (t > mc.thr) { t = 0.f; filtered = true; }
+                } else if constexpr (MK == MG_CURR) {
+                    t = curr_negative(t, curr_thr, curr_t, slope);
                 }
                 const float zz = t * mc.s;
                 if (FWD) {
@@ -478,11 +490,12 @@ __global__ void head_loss_kernel(const float* __restrict__ q, int N, float* __re
 }
 
 // the margin a launch runs with: the variant (mk, filt) and its kernel argument, ex for the descriptor variants, rows for MG_ROWS
-struct HeadMargin { int mk; bool filt; MarginConstEx ex; MarginRows rows; };
+struct HeadMargin { int mk; bool filt; MarginConstEx ex; MarginRows rows; MarginCurr curr; };
 
 template <int MK, bool FILT>
 static MarginArg<MK, FILT> margin_arg(const HeadMargin& hm) {
     if constexpr (MK == MG_ROWS) return hm.rows;
+    else if constexpr (MK == MG_CURR) return hm.curr;
     else return hm.ex;                              // plain ArcFace: the MarginConst part only
 }
 
@@ -534,6 +547,7 @@ static int head_launch(int dtype, const NtGeom& g, const HeadArgs& a, const Head
     HEAD_VARIANT(MG_COS, false)
     HEAD_VARIANT(MG_COS, true)
     HEAD_VARIANT(MG_ROWS, false)
+    HEAD_VARIANT(MG_CURR, false)
 #undef HEAD_VARIANT
     set_error("head: unknown margin variant %d", hm.mk);
     return FRHIP_EINVAL;
@@ -597,7 +611,19 @@ static int margin_desc(const frhip_margin_rows_t* mg, HeadMargin& hm, const char
     return FRHIP_OK;
 }
 
-// The eight forward / recompute entry points.  D: frhip_margin_t or frhip_margin_rows_t.  sub = false: head_kernel (K is not read);
+static int margin_desc(const frhip_margin_curr_t* mg, HeadMargin& hm, const char* who) {
+    if (!margin_curr_desc_ok(mg)) {
+        set_error("%s: bad CurricularFace descriptor (null descriptor, null thr or t, or m outside [0, pi))", who);
+        return FRHIP_EINVAL;
+    }
+    static_cast<MarginConst&>(hm.curr) = margin_const(mg->s, mg->m);
+    hm.curr.thr = mg->thr; hm.curr.t = mg->t;
+    hm.mk = MG_CURR;
+    hm.filt = false;
+    return FRHIP_OK;
+}
+
+// The forward / recompute entry points.  D: frhip_margin_t, frhip_margin_rows_t or frhip_margin_curr_t.  sub = false: head_kernel (K is not read);
 // sub = true: head_sub_kernel over K planes, K = 1 included.  Every argument is validated before anything is launched.
 template <typename D>
 static int head_fwd_impl(const char* who, int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
@@ -848,6 +874,37 @@ extern "C" int frhip_head_bwd_dt_sub_rows(int dtype, const void* ehat, const voi
     return head_bwd_dt_impl("frhip_head_bwd_dt_sub_rows", dtype, ehat, what, labels, n, classes, d, true, subcenters, margin, rowmax,
                             rowsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
 }
+
+// ---- CurricularFace: the four of the per-row margins with its descriptor
+extern "C" int frhip_head_fwd_curr(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                                   int d, const frhip_margin_curr_t* margin, float* part_max, float* part_sum, float* ztarget,
+                                   float* rowmax, float* rowsum, hipStream_t stream) {
+    return head_fwd_impl("frhip_head_fwd_curr", dtype, ehat, what, labels, n, classes, d, false, 1, margin, part_max, part_sum, ztarget,
+                         nullptr, rowmax, rowsum, stream);
+}
+
+extern "C" int frhip_head_fwd_sub_curr(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                                       int subcenters, const frhip_margin_curr_t* margin, float* part_max, float* part_sum,
+                                       float* ztarget, int* tsub, float* rowmax, float* rowsum, hipStream_t stream) {
+    return head_fwd_impl("frhip_head_fwd_sub_curr", dtype, ehat, what, labels, n, classes, d, true, subcenters, margin, part_max,
+                         part_sum, ztarget, tsub, rowmax, rowsum, stream);
+}
+
+extern "C" int frhip_head_bwd_dt_curr(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                                      int d, const frhip_margin_curr_t* margin, const float* rowmax, const float* rowsum, float gscale,
+                                      const float* upstream, void* dt, int ldt, void* dtt, int ldtt, hipStream_t stream) {
+    return head_bwd_dt_impl("frhip_head_bwd_dt_curr", dtype, ehat, what, labels, n, classes, d, false, 1, margin, rowmax, rowsum, gscale,
+                            upstream, dt, ldt, 0, dtt, ldtt, stream);
+}
+
+extern "C" int frhip_head_bwd_dt_sub_curr(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                                          int subcenters, const frhip_margin_curr_t* margin, const float* rowmax, const float* rowsum,
+                                          float gscale, const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt,
+                                          hipStream_t stream) {
+    return head_bwd_dt_impl("frhip_head_bwd_dt_sub_curr", dtype, ehat, what, labels, n, classes, d, true, subcenters, margin, rowmax,
+                            rowsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
+}
+
 extern "C" int frhip_l2norm_rows(int dtype, const float* x, void* xhat, float* norms, int rows, int d, float eps,
                                  hipStream_t stream) {
     return by_dtype(dtype, "frhip_l2norm_rows", [&](auto t) {

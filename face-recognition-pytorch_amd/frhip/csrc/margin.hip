@@ -107,6 +107,37 @@ __global__ __launch_bounds__(256) void margin_bwd_rows_kernel(const float* __res
     }
 }
 
+// CurricularFace (frhip_margin_curr_t) on explicit logits: the element rules of the head's MG_CURR variant (margin_shared.h).  NOT in
+// place: the backward rebuilds the clamp and the hard mask from the caller's untouched cosines.
+__global__ __launch_bounds__(256) void margin_fwd_curr_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                              int C, MarginConst mc, const float* __restrict__ thr,
+                                                              const float* __restrict__ tptr, float* __restrict__ out) {
+    const int row = blockIdx.x;
+    const int64_t lab = labels[row];
+    const float row_thr = thr[row], tt = tptr[0];
+    for (int j = threadIdx.x; j < C; j += 256) {
+        float t = fminf(fmaxf(logits[(size_t)row * C + j], -1.f), 1.f), slope;
+        t = j == lab ? curr_target(t, mc, slope) : curr_negative(t, row_thr, tt, slope);
+        out[(size_t)row * C + j] = t * mc.s;
+    }
+}
+
+__global__ __launch_bounds__(256) void margin_bwd_curr_kernel(const float* __restrict__ gout, const float* __restrict__ logits,
+                                                              const int64_t* __restrict__ labels, int C, MarginConst mc,
+                                                              const float* __restrict__ thr, const float* __restrict__ tptr,
+                                                              float* __restrict__ gin) {
+    const int row = blockIdx.x;
+    const int64_t lab = labels[row];
+    const float row_thr = thr[row], tt = tptr[0];
+    for (int j = threadIdx.x; j < C; j += 256) {
+        const float raw = logits[(size_t)row * C + j], t = fminf(fmaxf(raw, -1.f), 1.f);
+        float slope;
+        if (j == lab) curr_target(t, mc, slope);
+        else curr_negative(t, row_thr, tt, slope);
+        gin[(size_t)row * C + j] = (raw >= -1.f && raw <= 1.f) ? gout[(size_t)row * C + j] * mc.s * slope : 0.f;
+    }
+}
+
 __global__ __launch_bounds__(256) void rows_max_kernel(const float* __restrict__ x, int C, float* __restrict__ rowmax) {
     __shared__ float red[4];
     const float* r = x + (size_t)blockIdx.x * C;
@@ -217,6 +248,32 @@ extern "C" int frhip_margin_bwd_rows(const float* gout, const float* logits, con
     hipLaunchKernelGGL(margin_bwd_rows_kernel, dim3(n), dim3(256), 0, stream, gout, logits, labels, c, margin->s, margin->eps,
                        margin->m_ang, margin->m_add, gin);
     return check_launch("frhip_margin_bwd_rows");
+}
+
+static int margin_curr_args(const frhip_margin_curr_t* mg, const void* a, const void* b, const void* c, const void* d, const char* who) {
+    if (!margin_curr_desc_ok(mg) || !a || !b || !c || !d) {
+        set_error("%s: null pointer (an operand, the descriptor, its thr or t), or m outside [0, pi)", who);
+        return FRHIP_EINVAL;
+    }
+    return FRHIP_OK;
+}
+
+extern "C" int frhip_margin_fwd_curr(const float* logits, const int64_t* labels, int n, int c, const frhip_margin_curr_t* margin,
+                                     float* out, hipStream_t stream) {
+    if (margin_curr_args(margin, logits, labels, out, out, "frhip_margin_fwd_curr")) return FRHIP_EINVAL;
+    if (n <= 0) return FRHIP_OK;
+    hipLaunchKernelGGL(margin_fwd_curr_kernel, dim3(n), dim3(256), 0, stream, logits, labels, c, margin_const(margin->s, margin->m),
+                       margin->thr, margin->t, out);
+    return check_launch("frhip_margin_fwd_curr");
+}
+
+extern "C" int frhip_margin_bwd_curr(const float* gout, const float* logits, const int64_t* labels, int n, int c,
+                                     const frhip_margin_curr_t* margin, float* gin, hipStream_t stream) {
+    if (margin_curr_args(margin, gout, logits, labels, gin, "frhip_margin_bwd_curr")) return FRHIP_EINVAL;
+    if (n <= 0) return FRHIP_OK;
+    hipLaunchKernelGGL(margin_bwd_curr_kernel, dim3(n), dim3(256), 0, stream, gout, logits, labels, c, margin_const(margin->s, margin->m),
+                       margin->thr, margin->t, gin);
+    return check_launch("frhip_margin_bwd_curr");
 }
 
 extern "C" int frhip_rows_max(const float* x, int n, int c, float* rowmax, hipStream_t stream) {

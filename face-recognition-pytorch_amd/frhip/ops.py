@@ -806,6 +806,25 @@ def _margin_rows_desc(margin, n):
     return _MarginRowsDesc(float(margin.s), float(margin.eps), _p(margin.m_ang), _p(margin.m_add))
 
 
+class _MarginCurrDesc(ctypes.Structure):
+    _fields_ = [("s", ctypes.c_float), ("m", ctypes.c_float), ("thr", ctypes.c_void_p), ("t", ctypes.c_void_p)]
+
+
+def _is_curr(margin):
+    """CurricularFace (frhip_margin_curr_t), e.g. nets.ArcFace.CurrRows: fields s, m, the device vector thr [n] fp32 and the device scalar t"""
+    return hasattr(margin, "thr")
+
+
+def _margin_curr_desc(margin, n):
+    _need_cuda("CurricularFace margin", thr=margin.thr, t=margin.t)
+    if margin.thr.dtype != torch.float32 or margin.thr.numel() != n or not margin.thr.is_contiguous():
+        raise ValueError("CurricularFace thresholds must be a contiguous float32 vector with one entry per row (%d), got %s %s"
+                         % (n, margin.thr.dtype, tuple(margin.thr.shape)))
+    if margin.t.dtype != torch.float32 or margin.t.numel() != 1:
+        raise ValueError("CurricularFace's t must be one float32 element, got %s %s" % (margin.t.dtype, tuple(margin.t.shape)))
+    return _MarginCurrDesc(float(margin.s), float(margin.m), _p(margin.thr), _p(margin.t))
+
+
 def adaface_margins(norms, m, h, t_alpha, eps, batch_mean, batch_std, update):
     """AdaFace's per-row margins (m_ang, m_add) from the embedding norms [n] of the global batch in ONE launch (frhip_adaface_margins);
     update: the running batch_mean / batch_std (device scalars, fp32) are advanced in place first, else only read.  No host sync."""
@@ -931,6 +950,23 @@ def elastic_assign(tcos, g, kind):
     return out[0], out[1]
 
 
+def curricular_rows(tcos, m, alpha, t, update):
+    """CurricularFace's per-row thresholds in ONE launch (frhip_curricular_rows): tcos [world_size, n] (or [n]) target cosines of all ranks
+    (-2 where a rank does not own the row) -> thr [n] = cos(theta_y + m) of the merged cosine, +2 for a row nobody owns.  t: device scalar
+    (fp32), the running mean of the target cosines; update: t <- alpha mean + (1 - alpha) t in the same launch, else t is not touched.
+    No host sync."""
+    _need_f32("curricular_rows", tcos=tcos, t=t)
+    tcos = tcos.reshape(1, -1) if tcos.dim() == 1 else tcos
+    if tcos.dim() != 2 or tcos.shape[1] < 1 or not tcos.is_contiguous() or t.numel() != 1:
+        raise ValueError("curricular_rows: tcos must be [world_size, n] (contiguous, n >= 1) and t one element, got %s, %s"
+                         % (tuple(tcos.shape), tuple(t.shape)))
+    n = tcos.shape[1]
+    thr = torch.empty((n,), dtype=torch.float32, device=tcos.device)
+    check(lib().frhip_curricular_rows(_p(tcos), tcos.shape[0], n, float(m), float(alpha), int(bool(update)), _p(t), _p(thr), _s()),
+          "frhip_curricular_rows")
+    return thr
+
+
 def head_sub_max():
     """the largest number of sub-centres per class the head kernels serve"""
     return lib().frhip_head_sub_max()
@@ -949,12 +985,15 @@ def _head_margin(margin, s, m, n, k):
         return "", None
     if margin is not None and _is_rows(margin):
         return "_rows", _margin_rows_desc(margin, n)
+    if margin is not None and _is_curr(margin):
+        return "_curr", _margin_curr_desc(margin, n)
     return ("" if k > 1 else "_ex"), _margin_desc((MARGIN_ARCFACE, 0, s, m, 0.0) if margin is None else margin)
 
 
 def head_fwd(ehat, what, labels_i32, s, m, margin=None, subcenters=1):
     """margin=None: ArcFace(s, m) (frhip_head_fwd); a (kind, easy, s, m, filter_thr) descriptor (frhip_head_fwd_ex); or per-row
-    margins (s, eps, m_ang, m_add), e.g. nets.ArcFace.RowMargins (frhip_head_fwd_rows).
+    margins (s, eps, m_ang, m_add), e.g. nets.ArcFace.RowMargins (frhip_head_fwd_rows); or CurricularFace's (s, m, thr, t), e.g.
+    nets.ArcFace.CurrRows (frhip_head_fwd_curr).
     subcenters = K > 1 (frhip_head_fwd_sub / _sub_rows): what holds K x classes rows, plane-major (row k * classes + c); a class's cosine is
     the maximum over its K centres and the result gains tsub [n] int32, the winning centre of each row's target (-1: no target on this shard)."""
     k = _check_subcenters(what, subcenters)
@@ -1132,6 +1171,26 @@ def margin_bwd_rows(gout, logits, labels_i64, margin):
     gin = torch.empty_like(gout)
     check(lib().frhip_margin_bwd_rows(_p(gout), _p(logits), _p(labels_i64), n, c, ctypes.byref(desc), _p(gin), _s()),
           "frhip_margin_bwd_rows")
+    return gin
+
+
+def margin_fwd_curr(logits, labels_i64, margin):
+    """out [n, c] = s x CurricularFace of the cosines `logits` (margin: s, m, thr [n], t; frhip_margin_fwd_curr); logits stay untouched"""
+    n, c = logits.shape
+    _need_f32("margin_fwd_curr", logits=logits)
+    desc = _margin_curr_desc(margin, n)
+    out = torch.empty_like(logits)
+    check(lib().frhip_margin_fwd_curr(_p(logits), _p(labels_i64), n, c, ctypes.byref(desc), _p(out), _s()), "frhip_margin_fwd_curr")
+    return out
+
+
+def margin_bwd_curr(gout, logits, labels_i64, margin):
+    n, c = gout.shape
+    _need_f32("margin_bwd_curr", gout=gout, logits=logits)
+    desc = _margin_curr_desc(margin, n)
+    gin = torch.empty_like(gout)
+    check(lib().frhip_margin_bwd_curr(_p(gout), _p(logits), _p(labels_i64), n, c, ctypes.byref(desc), _p(gin), _s()),
+          "frhip_margin_bwd_curr")
     return gin
 
 

@@ -12,6 +12,8 @@ tensor and leaves `logits` untouched.  `MagFace(s, m, u_margin, l_a, u_a, lambda
 same with a margin that grows with the norm; its regulariser and the gradient through the norms live in the fused head.
 `ElasticFace(s, m, std, kind, plus, seed)` (Boutros et al., CVPR-W 2022; not in the reference) draws every row's margin from N(m, std) at
 every step, and with `plus` hands the draws out by difficulty: `forward(logits, labels)`, a new tensor as well.
+`CurricularFace(s, m, alpha)` (Huang et al., CVPR 2020; not in the reference) re-weights the hard NEGATIVES of every row by a running mean
+of the target cosines: `forward(logits, labels)`, a new tensor as well.
 
 Inside PartialFC the margin is not applied through this `forward`: it lives in the epilogue of the fused cos-theta
 MFMA kernel (frhip_head_fwd / frhip_head_fwd_ex), which only reads the module's constants through `margin_of`, so the
@@ -39,13 +41,22 @@ MagMargin = collections.namedtuple("MagMargin", "s m u_margin l_a u_a lambda_g e
 # the key of the generator); the kernels take RowMargins, filled by frhip_elastic_margins or frhip_elastic_draws + frhip_elastic_assign
 ElasticMargin = collections.namedtuple("ElasticMargin", "s m std kind plus seed eps")
 
-SUPPORTED = "ArcFace, CosFace, CombinedMarginLoss (ArcFace m1 == 1, m3 == 0 or CosFace m3 > 0), AdaFace, MagFace, ElasticFace"
+# CurricularFace: the constants of the module (m: the margin, alpha: the momentum of t), and what the kernels take once
+# frhip_curricular_rows has turned the batch's target cosines into thresholds: scale, margin, the device vector thr [N] and the device
+# scalar t (frhip_margin_curr_t)
+CurricularMargin = collections.namedtuple("CurricularMargin", "s m alpha")
+CurrRows = collections.namedtuple("CurrRows", "s m thr t")
+
+SUPPORTED = ("ArcFace, CosFace, CombinedMarginLoss (ArcFace m1 == 1, m3 == 0 or CosFace m3 > 0), AdaFace, MagFace, ElasticFace, "
+             "CurricularFace")
 
 
 def margin_of(module):
     """-> Margin of a margin module of this package, read from its attributes NOW (so a later `easy_margin = True` counts, as in
     the reference, whose modules read their attributes in forward); AdaMargin for AdaFace, MagMargin for MagFace, ElasticMargin for
-    ElasticFace.  NotImplementedError for any other module."""
+    ElasticFace, CurricularMargin for CurricularFace.  NotImplementedError for any other module."""
+    if isinstance(module, CurricularFace):
+        return CurricularMargin(float(module.s), float(module.m), float(module.alpha))
     if isinstance(module, ElasticFace):
         return ElasticMargin(float(module.s), float(module.m), float(module.std), module.kind, bool(module.plus), int(module.seed),
                              float(module.eps))
@@ -326,3 +337,69 @@ class _HipElastic:
     def elastic_assign(tcos, g, mg):
         from frhip import ops
         return ops.elastic_assign(tcos.float().contiguous(), g, mg.kind)
+
+
+class _CurrFn(torch.autograd.Function):
+    """CurricularFace on explicit logits (frhip_margin_fwd_curr / _bwd_curr); no gradient to the thresholds or t"""
+
+    @staticmethod
+    def forward(ctx, logits, labels, rows):
+        from frhip import ops
+        if not logits.is_cuda:
+            raise RuntimeError("nets.ArcFace (frhip): logits must live on the MI355X; there is no CPU path")
+        lab = labels.reshape(-1).long().contiguous()
+        # t is kept by value: the module advances its buffer in place at the next call, and the mask is rebuilt from this step's
+        ctx.save_for_backward(logits, lab, rows.thr, rows.t.clone())
+        ctx.s, ctx.m = rows.s, rows.m
+        return ops.margin_fwd_curr(logits.detach().float().contiguous(), lab, rows)
+
+    @staticmethod
+    def backward(ctx, g):
+        from frhip import ops
+        logits, lab, thr, t = ctx.saved_tensors
+        return ops.margin_bwd_curr(g.contiguous().float(), logits.detach().float().contiguous(), lab, CurrRows(ctx.s, ctx.m, thr, t)), None, None
+
+
+class CurricularFace(torch.nn.Module):
+    """Adaptive curriculum (CurricularFace, Huang et al., CVPR 2020; the official implementation's rule): the target logit is ArcFace's,
+    s cos(theta_y + m) above cos(pi - m) and s (cos(theta_y) - m sin(pi - m)) below; a NON-target cosine c of row i that is above the row's
+    own cos(theta_y + m) -- a hard negative -- becomes s c (t + c), every other one s c.  t is a running mean of the GLOBAL batch's target
+    cosines (momentum alpha; a device buffer, checkpointed, starts at 0), advanced in training mode BEFORE it is used and only read in
+    eval mode: hard negatives weigh little early in training and more later.  Every cosine is clamped to [-1, 1] first; no gradient
+    flows through the thresholds or t."""
+    kind = "curricularface"
+
+    def __init__(self, s=64.0, m=0.5, alpha=0.01):
+        super().__init__()
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError("CurricularFace: alpha must lie in [0, 1], got %r" % (alpha,))
+        if not 0.0 <= m < math.pi:
+            raise ValueError("CurricularFace: m must lie in [0, pi), got %r" % (m,))
+        self.s, self.m, self.alpha = s, m, alpha
+        self.scale, self.margin = s, m
+        self.register_buffer("t", torch.zeros(1))
+
+    def row_thresholds(self, tcos, kernels=None):
+        """tcos ([world_size, n] or [n], detached; -2 where a rank does not own the row): the rows' target cosines -> CurrRows; in
+        training mode t is advanced first.  ONE launch of frhip_curricular_rows, no host synchronisation.  kernels: PartialFC's kernel
+        object (tests swap in a double)."""
+        mg = margin_of(self)
+        tcos = tcos.detach()
+        tcos = tcos.reshape(1, -1) if tcos.dim() == 1 else tcos
+        fn = kernels.curricular_rows if kernels is not None else _hip_curricular_rows
+        return CurrRows(mg.s, mg.m, fn(tcos, mg, self.t, self.training), self.t)
+
+    def forward(self, logits: torch.Tensor, labels: torch.Tensor):
+        """The loss's logits from explicit cosines [N, C] (labels [N] or [N, 1], -1 = no target): -> the scaled logits, a new tensor like
+        AdaFace.forward, differentiable in `logits`.  The target cosines are read off `logits`."""
+        lab = labels.reshape(-1).long()
+        if self.t.device != logits.device:
+            raise RuntimeError("nets.ArcFace (frhip): CurricularFace's t buffer must live on the logits' device: module.to(device)")
+        picked = logits.detach().float().gather(1, lab.clamp(min=0).view(-1, 1)).view(-1)
+        tcos = torch.where(lab >= 0, picked, torch.full_like(picked, -2.0)).contiguous()
+        return _CurrFn.apply(logits, labels, self.row_thresholds(tcos))
+
+
+def _hip_curricular_rows(tcos, mg, t, update):
+    from frhip import ops
+    return ops.curricular_rows(tcos.float().contiguous(), mg.m, mg.alpha, t, update)

@@ -24,7 +24,9 @@ What runs where
     (frhip_magface_margins: margins and regulariser in one launch) and returns d loss / d norm of its own rows from the statistics every
     rank already holds (frhip_magface_norm_grad), with no further collective.  ElasticFace draws its per-row margins on every rank from
     (seed, step, row) with no collective at all (frhip_elastic_margins); its "+" variants add one all-gather of the rows' target cosines
-    ([N] floats per rank, frhip_head_target_cos), which every rank merges and ranks itself (frhip_elastic_assign).
+    ([N] floats per rank, frhip_head_target_cos), which every rank merges and ranks itself (frhip_elastic_assign).  CurricularFace
+    gathers the same target cosines and turns them into per-row thresholds and its running mean t on every rank (frhip_curricular_rows,
+    one launch).
 `conf.subcenters = K` (not in the reference; sub-center ArcFace): every class owns K centres, the table is plane-major [K x num_local, D]
 (centre k of class c in row k * num_local + c), the fused kernels take the maximum over a class's centres on their accumulators and send
 its gradient to the winner alone; sampling, sharding and the collectives stay at class level.  Absent or 1: the calls made before.
@@ -38,8 +40,8 @@ from typing import Callable
 import torch
 from torch import distributed
 
-from .ArcFace import (SUPPORTED as SUPPORTED_MARGINS, AdaFace, AdaMargin, ArcFace, CombinedMarginLoss, CosFace, ElasticFace, ElasticMargin,
-                      MagFace, MagMargin, RowMargins, is_plain_arcface, margin_of)
+from .ArcFace import (SUPPORTED as SUPPORTED_MARGINS, AdaFace, AdaMargin, ArcFace, CombinedMarginLoss, CosFace, CurricularFace,
+                      CurricularMargin, CurrRows, ElasticFace, ElasticMargin, MagFace, MagMargin, RowMargins, is_plain_arcface, margin_of)
 
 
 import os
@@ -92,6 +94,11 @@ class HipHeadKernels:
     def elastic_assign(self, tcos, g, mg):
         """tcos [ws, n] of all ranks, g [n] -> (m_ang, m_add): the r-th largest cosine gets the r-th smallest draw"""
         return self.ops.elastic_assign(tcos, g, mg.kind)
+
+    def curricular_rows(self, tcos, mg, t, update):
+        """tcos [ws, n] of all ranks -> thr [n]: CurricularFace's per-row thresholds; update: t is advanced in the same launch.
+        mg: nets.ArcFace.CurricularMargin"""
+        return self.ops.curricular_rows(tcos, mg.m, mg.alpha, t, update)
 
     def rescale(self, rowsum, local_max, global_max):
         self.ops.head_rescale(rowsum, local_max, global_max)
@@ -206,7 +213,7 @@ class _MarginSoftmaxFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, local_embeddings, weight_activated, labels_i32, kern, s, m, world_size, collectives, margin=None, adaface=None,
-                subcenters=1, sub_out=None, magface=None, local_norms=None, elastic=None):
+                subcenters=1, sub_out=None, magface=None, local_norms=None, elastic=None, curricular=None):
         """adaface: None, or (AdaFace module, this rank's norms [rows]) -- the per-row margins are then derived here, from the norms of
         the global batch in rank order, and `margin` is ignored.
         subcenters = K > 1: weight_activated holds K x classes rows, plane-major; the winning centre of every row's target (int32 [N], -1
@@ -216,7 +223,9 @@ class _MarginSoftmaxFn(torch.autograd.Function):
         rank's norms when they require one
         elastic: None, or the ElasticFace module: the per-row margins are drawn here (every rank draws the whole global batch's); with
         `plus` in training mode the rows' target cosines are computed from the normalised operands, all-gathered ([rows] floats per rank)
-        and ranked first.  `margin` is ignored"""
+        and ranked first.  `margin` is ignored
+        curricular: None, or the CurricularFace module: the rows' target cosines are computed and all-gathered the same way (in eval mode
+        too: the thresholds need them) and turned into per-row thresholds; t is advanced in training mode.  `margin` is ignored"""
         local_embeddings = local_embeddings.contiguous()
         rows, dim = local_embeddings.shape
         if collectives:                                                         # :182 (C1)
@@ -252,6 +261,14 @@ class _MarginSoftmaxFn(torch.autograd.Function):
             rm = elastic.row_margins(kern, tcos, n=ehat.shape[0])
             extra, row_vecs = {"margin": rm}, (rm.m_ang, rm.m_add)
             ctx.row_consts = (rm.s, rm.eps)
+        ctx.curr = None
+        if curricular is not None:
+            mine = kern.head_target_cos(ehat, what, labels_i32, subcenters)
+            tcos = _all_gather_flat(mine.new_empty(world_size * mine.numel()), mine) if collectives else mine
+            cr = curricular.row_thresholds(tcos.view(-1, mine.numel()), kern)       # ONE launch; advances t in training mode
+            # t by value for the backward: the buffer moves on at the next forward, the mask must be rebuilt from this step's
+            extra, row_vecs = {"margin": cr}, (cr.thr, cr.t.clone())
+            ctx.curr = (cr.s, cr.m)
         if subcenters > 1:                                   # one centre per class: the calls made before sub-centres existed
             zt, rmax, rsum, tsub = kern.forward_stats(ehat, what, labels_i32, s, m, subcenters=subcenters, **extra)
             if sub_out is not None:
@@ -283,11 +300,14 @@ class _MarginSoftmaxFn(torch.autograd.Function):
         ehat, enorm, what, wnorm, labels_i32, rmax, rsum, *row_vecs = ctx.saved_tensors
         if ctx.mag is not None:
             row_vecs, ctx.mag_saved = row_vecs[:2], row_vecs[2:]
-        extra = dict({"margin": RowMargins(*ctx.row_consts, *row_vecs)} if row_vecs else ctx.extra, **ctx.sub)
+        if ctx.curr is not None:
+            extra = dict({"margin": CurrRows(*ctx.curr, *row_vecs)}, **ctx.sub)
+        else:
+            extra = dict({"margin": RowMargins(*ctx.row_consts, *row_vecs)} if row_vecs else ctx.extra, **ctx.sub)
         up = grad_loss.reshape(1).float().contiguous()
         if not ctx.collectives:
             d_e, d_w = ctx.kern.backward(ehat, enorm, what, wnorm, labels_i32, ctx.s, ctx.m, rmax, rsum, ehat.shape[0], up, **extra)
-            return (d_e, d_w) + (None,) * 11 + (_MarginSoftmaxFn._norm_grad(ctx, rmax, rsum, up, 0, 1.0), None)
+            return (d_e, d_w) + (None,) * 11 + (_MarginSoftmaxFn._norm_grad(ctx, rmax, rsum, up, 0, 1.0), None, None)
         # :504-522 (C6): reduce-scatter(SUM) of dE, x world_size (folded into the normalise-backward's scale); issued as soon
         # as dE is enqueued so that it runs beside the dW GEMM
         pending = []
@@ -301,7 +321,7 @@ class _MarginSoftmaxFn(torch.autograd.Function):
         d_local, work = pending[0]
         if work is not None:
             work.wait()
-        return (d_local, d_w) + (None,) * 11 + (_MarginSoftmaxFn._norm_grad(ctx, rmax, rsum, up, rank, float(ctx.world_size)), None)
+        return (d_local, d_w) + (None,) * 11 + (_MarginSoftmaxFn._norm_grad(ctx, rmax, rsum, up, rank, float(ctx.world_size)), None, None)
 
     @staticmethod
     def _norm_grad(ctx, rmax, rsum, up, rank, scale):
@@ -397,7 +417,7 @@ class _PartialFCBase(torch.nn.Module):
             self.margin_softmax = margin_loss(conf.loss_s, conf.loss_m)
         else:
             raise
-        if not isinstance(self.margin_softmax, (ArcFace, CosFace, CombinedMarginLoss, AdaFace, MagFace, ElasticFace)):
+        if not isinstance(self.margin_softmax, (ArcFace, CosFace, CombinedMarginLoss, AdaFace, MagFace, ElasticFace, CurricularFace)):
             raise NotImplementedError("the fused head kernel implements the margin modules %s, not %s"
                                       % (SUPPORTED_MARGINS, type(self.margin_softmax).__name__))
         self._kernels = kernels
@@ -653,6 +673,8 @@ class _PartialFCBase(torch.nn.Module):
             tail = (None, None, 1, None, self.margin_softmax, norms)
         if isinstance(mg, ElasticMargin):                        # the margins are drawn inside the node, from the module's step counter
             tail = (None, None, 1, None, None, None, self.margin_softmax)
+        if isinstance(mg, CurricularMargin):                     # thresholds and t are derived inside the node, from the target cosines
+            tail = (None, None, 1, None, None, None, None, self.margin_softmax)
         if ready is not None and ready.numel() == n_global:      # everything label-side was done by prepare()
             return self._margin_softmax(local_embeddings, ready, s, m, collectives, tail)
         n_pos = None
@@ -764,6 +786,10 @@ class _PartialFCBase(torch.nn.Module):
                     buf.copy_(src.to(buf.device).reshape(buf.shape)) if src is not None else buf.fill_(init)
         if isinstance(self.margin_softmax, ElasticFace):          # the step counter of the draws; a checkpoint without it starts at 0
             buf, src = self.margin_softmax.step, state_dict.get("margin_softmax.step")
+            with torch.no_grad():
+                buf.copy_(src.to(buf.device).reshape(buf.shape)) if src is not None else buf.zero_()
+        if isinstance(self.margin_softmax, CurricularFace):       # the running mean of the target cosines; a checkpoint without it starts at 0
+            buf, src = self.margin_softmax.t, state_dict.get("margin_softmax.t")
             with torch.no_grad():
                 buf.copy_(src.to(buf.device).reshape(buf.shape)) if src is not None else buf.zero_()
         rows = self.subcenters * self.num_local

@@ -467,6 +467,45 @@ int frhip_elastic_assign_workspace(int n);
 int frhip_elastic_assign(const float* tcos, int world_size, int n, const float* g, int kind, float* m_ang, float* m_add, void* work,
                          size_t work_bytes, frhip_stream_t stream);
 
+/* CurricularFace (not in the reference: Huang et al., CVPR 2020; the official implementation's rule).  The one margin that changes the
+ * NON-target logits, by a test that depends on the row.  Global batch of n rows, scale s, margin m with cos_m, sin_m,
+ * theta = cos(pi - m), sinmm = m sin(pi - m) rounded once from float64, momentum alpha (0.01), module state a scalar t that starts at 0:
+ *   every cosine c = clamp(raw, -1, 1), gradient 0 where the clamp binds (as in the ArcFace variant);
+ *   c_i = row i's target cosine: the maximum over the ranks of the frhip_head_target_cos vectors (-2 where a rank does not own the row),
+ *         clamped to [-1, 1];
+ *   thr_i = c_i cos_m - sqrt(1 - c_i^2) sin_m = cos(theta_y + m), with no fallback branch (the official mask uses it this way);
+ *   a row that no rank owns (c_i = -2 after the maximum, or NaN) gets thr_i = +2: nothing in it is hard;
+ *   training: t <- alpha mean(c_i over the owned rows) + (1 - alpha) t BEFORE t is used (no owned row: t unchanged); eval: t is only read;
+ *   target column: ArcFace's rule -- c > theta: s cos(theta_y + m), slope s (cos_m + c sin_m / sqrt(1 - c^2)); else s (c - sinmm), slope s --
+ *         applied to the cosine the head kernel itself computed;
+ *   non-target column of row i: c > thr_i (strictly): logit s c (t + c), d/dc = s (t + 2 c); otherwise logit s c, d/dc = s;
+ *   a row whose label is -1 on this shard has no exempt column: its negatives use the thr_i the owning rank produced;
+ *   no gradient flows through thr_i or t;
+ *   with K sub-centres the pooled cosine (maximum over the class's centres) is compared and scaled, the gradient goes to the winner alone.
+ * frhip_curricular_rows: tcos [world_size][n] -> thr[n], ONE launch of one workgroup, no host synchronisation (capturable).  The mean is
+ * summed in float64 in an order fixed by n (every rank gets the same bits without a collective); thr is evaluated in float64 and rounded
+ * once.  t: device scalar (fp32); update != 0: read, advanced and written back by this same launch; update == 0: not touched.
+ * n < 1, world_size < 1, a null pointer, m outside [0, pi) or alpha outside [0, 1]: FRHIP_EINVAL, nothing is launched. */
+int frhip_curricular_rows(const float* tcos, int world_size, int n, double m, double alpha, int update, float* t, float* thr,
+                          frhip_stream_t stream);
+/* The head with that rule: thr [n] from frhip_curricular_rows, t the device scalar (read by the kernels at run time, so a captured
+ * graph sees each step's value).  Signatures of the _rows / _sub_rows entry points.  A null descriptor or pointer in it, or m outside
+ * [0, pi): FRHIP_EINVAL, nothing is launched. */
+typedef struct { float s, m; const float* thr; const float* t; } frhip_margin_curr_t;
+int frhip_head_fwd_curr(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                        int d, const frhip_margin_curr_t* margin, float* part_max, float* part_sum, float* ztarget,
+                        float* rowmax, float* rowsum, frhip_stream_t stream);
+int frhip_head_bwd_dt_curr(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes,
+                           int d, const frhip_margin_curr_t* margin, const float* rowmax, const float* rowsum, float gscale,
+                           const float* upstream, void* dt, int ldt, void* dtt, int ldtt, frhip_stream_t stream);
+int frhip_head_fwd_sub_curr(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                            int subcenters, const frhip_margin_curr_t* margin, float* part_max, float* part_sum,
+                            float* ztarget, int* tsub, float* rowmax, float* rowsum, frhip_stream_t stream);
+int frhip_head_bwd_dt_sub_curr(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                               int subcenters, const frhip_margin_curr_t* margin, const float* rowmax, const float* rowsum,
+                               float gscale, const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt,
+                               frhip_stream_t stream);
+
 /* ---- bn1 -> relu -> conv2 of a BasicBlock (nets/resnet.py:91-93) WITHOUT the activated tensor: the BatchNorm-apply + ReLU
  * is folded into the operand path of the convolution (forward) and of its weight gradient, which read the saved BatchNorm
  * INPUT x and form relu(x * in_scale[c] + in_shift[c]) in LDS.  bf16, 3x3 / stride 1 / pad 1; *_fusable() tells whether a
@@ -561,6 +600,12 @@ int frhip_margin_fwd_rows(const float* logits, const int64_t* labels, int n, int
                           frhip_stream_t stream);
 int frhip_margin_bwd_rows(const float* gout, const float* logits, const int64_t* labels, int n, int c,
                           const frhip_margin_rows_t* margin, float* gin, frhip_stream_t stream);
+/* CurricularFace (frhip_margin_curr_t above; CurricularFace.forward stand-alone) on explicit cosines, thr [n] one threshold per row.
+ * NOT in place, like the _rows pair: the backward rebuilds the hard mask and the clamp from the caller's untouched logits. */
+int frhip_margin_fwd_curr(const float* logits, const int64_t* labels, int n, int c, const frhip_margin_curr_t* margin, float* out,
+                          frhip_stream_t stream);
+int frhip_margin_bwd_curr(const float* gout, const float* logits, const int64_t* labels, int n, int c,
+                          const frhip_margin_curr_t* margin, float* gin, frhip_stream_t stream);
 int frhip_rows_max(const float* x, int n, int c, float* rowmax, frhip_stream_t stream);
 int frhip_rows_exp_sum(float* x, int n, int c, const float* rowmax, float* rowsum, frhip_stream_t stream);
 int frhip_rows_normalize(float* x, int n, int c, const float* rowsum, const int64_t* labels, float* ptarget,
