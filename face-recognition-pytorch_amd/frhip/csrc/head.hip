@@ -13,6 +13,9 @@
 // magface_margins_kernel below; MagFace's gradient through the norms is magface_norm_grad_kernel and l2norm_bwd_norm*_kernel.
 // CurricularFace (MG_CURR, not in the reference) is the one variant that also changes the non-target elements by a per-row test; its
 // thresholds come from curricular_rows_kernel (curricular.hip).
+// The sigmoid head (MG_BCE: UniFace / SphereFace2, not in the reference) is no softmax at all: head_epilogue_bce below; what follows its
+// partials (row fold, rank pair, merge) is bce.hip.
+#include <type_traits>
 #include "igemm_nt.h"
 #include "margin_shared.h"
 #include "frhip.h"
@@ -25,13 +28,14 @@ struct MarginConstEx : MarginConst { float m3, thr; };       // CosFace margin, 
 // argument, so its kernel-argument layout and code are exactly those it had before the variants existed.
 // (named constants and a traits struct, not an unnamed enum in std::conditional: the kernels' mangled names must come out the same in the
 // host and the device compilation, and an unnamed type is numbered differently in the two)
-constexpr int MG_ARC = 0, MG_ARC_EASY = 1, MG_COS = 2, MG_ROWS = 3, MG_CURR = 4;
+constexpr int MG_ARC = 0, MG_ARC_EASY = 1, MG_COS = 2, MG_ROWS = 3, MG_CURR = 4, MG_BCE = 5;
 struct MarginRows { float s, eps; const float* m_ang; const float* m_add; };      // per-row margins: [M] angular, [M] additive
 struct MarginCurr : MarginConst { const float* thr; const float* t; };            // CurricularFace: [M] thresholds, the device scalar t
 template <int MK, bool FILT> struct MarginArgOf { typedef MarginConstEx type; };
 template <> struct MarginArgOf<MG_ARC, false> { typedef MarginConst type; };
 template <> struct MarginArgOf<MG_ROWS, false> { typedef MarginRows type; };
 template <> struct MarginArgOf<MG_CURR, false> { typedef MarginCurr type; };
+template <> struct MarginArgOf<MG_BCE, false> { typedef MarginBce type; };                // margin_shared.h
 template <int MK, bool FILT>
 using MarginArg = typename MarginArgOf<MK, FILT>::type;
 
@@ -166,6 +170,58 @@ __global__ __launch_bounds__(256) void l2norm_bwd_norm_kernel(const float* __res
     }
 }
 
+// The epilogue of the sigmoid (BCE) head, same tile and arguments as head_epilogue below (which hands MG_BCE over to it): every element is
+// a binary problem against the one threshold b = *mc.bias (read once per wave), rules bce_target / bce_negative of margin_shared.h.
+// FWD = true : part_loss / part_db [group][m] = this 64-class column group's sums of the loss terms and of the d/db terms of row m;
+//              ztarget[m] = a of the target; tsub as below.  Rows past M and classes past Nout add exactly 0: a padded column's cosine is
+//              0, and unmasked it would add softplus(-b) to the loss.
+// FWD = false: acc becomes d(loss)/d(cos) x gscale, from the element alone -- no row statistics are read; 0 where the clamp binds, in
+//              rows past M and classes past Nout.
+template <bool FWD, bool SUB>
+__device__ __forceinline__ void head_epilogue_bce(int lane, const NtGeom& g, f32x4_t (&acc)[4][4], const uint32_t* win, int m0, int n0,
+                                                  int group, const int* labels, const MarginBce& mc, float* part_loss, float* part_db,
+                                                  float* ztarget, int* tsub, float gscale, const float* upstream) {
+    const int fi = lane & 15, fg = lane >> 4;
+    if (!FWD && upstream) gscale *= upstream[0];
+    const float b = mc.bias[0];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+        const int m = m0 + mt * 16 + fi;
+        const bool mrow = m < g.M;
+        const int lab = mrow ? labels[m] : -1;
+        if constexpr (SUB)
+            if (FWD && group == 0 && fg == 0 && mrow && lab < 0) tsub[m] = -1;
+        float vl = 0.f, vd = 0.f;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int cls = n0 + nt * 16 + 4 * fg + e;
+                const float raw = acc[nt][mt][e], c = fminf(fmaxf(raw, -1.f), 1.f);
+                const bool tgt = cls == lab, live = cls < g.Nout && mrow;        // lab = -1 past M, and a label lies below Nout
+                float a, dcos, db;
+                const float term = tgt ? bce_target(c, mc, b, a, dcos, db) : bce_negative(c, mc, b, a, dcos, db);
+                if (FWD) {
+                    if (live) { vl += term; vd += db; }
+                    if (tgt) {
+                        ztarget[m] = a;
+                        if constexpr (SUB) tsub[m] = (int)((win[nt] >> (2 * (4 * mt + e))) & 3u);
+                    }
+                } else {
+                    acc[nt][mt][e] = (live && raw >= -1.f && raw <= 1.f) ? dcos * gscale : 0.f;
+                }
+            }
+        if (FWD) {
+            vl = lane_sum_bit5(lane_sum_bit4(vl));
+            vd = lane_sum_bit5(lane_sum_bit4(vd));
+            if (fg == 0 && mrow) {
+                part_loss[(size_t)group * g.M + m] = vl;
+                part_db[(size_t)group * g.M + m] = vd;
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // The epilogue of both head kernels, on one wave's 64 x 64 tile of cosines acc[nt][mt] (rows from m0, classes from n0).
 // FWD = true : partial row max / sum-exp per 64-class column group, target logit.
@@ -173,7 +229,8 @@ __global__ __launch_bounds__(256) void l2norm_bwd_norm_kernel(const float* __res
 // MK: MG_ARC (cos(theta + m), below cos(pi - m) t - m sin(pi - m)), MG_ARC_EASY (cos(theta + m) for t > 0, else t), MG_COS (t - m3),
 // MG_ROWS (row m: every cosine clamped to [-1 + eps, 1 - eps], target cos(clamp(theta + m_ang[m], eps, pi - eps)) - m_add[m], slope 0 where
 // a clamp binds; frhip_margin_rows_t in frhip.h), MG_CURR (the target as MG_ARC; a non-target of row m whose clamped cosine is > thr[m]
-// becomes t (tt + t), slope tt + 2 t, tt = *mc.t read once per wave; a label -1 row has no exempt column; frhip_margin_curr_t in frhip.h).
+// becomes t (tt + t), slope tt + 2 t, tt = *mc.t read once per wave; a label -1 row has no exempt column; frhip_margin_curr_t in frhip.h),
+// MG_BCE (no softmax: head_epilogue_bce above, with part_max / part_sum as its part_loss / part_db; rowmax / rowsum are not read).
 // FILT: interclass filtering (reference nets/ArcFace.py:28-39): an element that is not its row's target and whose clamped cosine is
 // > thr is multiplied by 0 -- logit 0, which still counts in the softmax sum, and d/dcos 0 (the reference builds the mask under
 // no_grad); a row without a target on this shard (label -1) is filtered in every column.
@@ -186,6 +243,10 @@ __device__ __forceinline__ void head_epilogue(int lane, const NtGeom& g, f32x4_t
                                               int group, const int* labels, MarginArg<MK, FILT> mc, float* part_max, float* part_sum,
                                               float* ztarget, int* tsub, const float* rowmax, const float* rowsum, float gscale,
                                               const float* upstream) {
+    if constexpr (MK == MG_BCE) {
+        head_epilogue_bce<FWD, SUB>(lane, g, acc, win, m0, n0, group, labels, mc, part_max, part_sum, ztarget, tsub, gscale, upstream);
+        return;
+    }
     const int fi = lane & 15, fg = lane >> 4;
     if (!FWD && upstream) gscale *= upstream[0];        // d(loss)/d(loss) stays on the device: no host sync
     [[maybe_unused]] float curr_t = 0.f, curr_thr = 2.f;                      // MG_CURR only
@@ -490,12 +551,13 @@ __global__ void head_loss_kernel(const float* __restrict__ q, int N, float* __re
 }
 
 // the margin a launch runs with: the variant (mk, filt) and its kernel argument, ex for the descriptor variants, rows for MG_ROWS
-struct HeadMargin { int mk; bool filt; MarginConstEx ex; MarginRows rows; MarginCurr curr; };
+struct HeadMargin { int mk; bool filt; MarginConstEx ex; MarginRows rows; MarginCurr curr; MarginBce bce; };
 
 template <int MK, bool FILT>
 static MarginArg<MK, FILT> margin_arg(const HeadMargin& hm) {
     if constexpr (MK == MG_ROWS) return hm.rows;
     else if constexpr (MK == MG_CURR) return hm.curr;
+    else if constexpr (MK == MG_BCE) return hm.bce;
     else return hm.ex;                              // plain ArcFace: the MarginConst part only
 }
 
@@ -548,6 +610,7 @@ static int head_launch(int dtype, const NtGeom& g, const HeadArgs& a, const Head
     HEAD_VARIANT(MG_COS, true)
     HEAD_VARIANT(MG_ROWS, false)
     HEAD_VARIANT(MG_CURR, false)
+    HEAD_VARIANT(MG_BCE, false)
 #undef HEAD_VARIANT
     set_error("head: unknown margin variant %d", hm.mk);
     return FRHIP_EINVAL;
@@ -623,7 +686,16 @@ static int margin_desc(const frhip_margin_curr_t* mg, HeadMargin& hm, const char
     return FRHIP_OK;
 }
 
-// The forward / recompute entry points.  D: frhip_margin_t, frhip_margin_rows_t or frhip_margin_curr_t.  sub = false: head_kernel (K is not read);
+static int margin_desc(const frhip_margin_bce_t* mg, HeadMargin& hm, const char* who) {
+    if (const char* why = margin_bce_desc_error(mg)) { set_error("%s: bad BCE descriptor: %s", who, why); return FRHIP_EINVAL; }
+    hm.bce = margin_bce(mg);
+    hm.mk = MG_BCE;
+    hm.filt = false;
+    return FRHIP_OK;
+}
+
+// The forward / recompute entry points.  D: frhip_margin_t, frhip_margin_rows_t, frhip_margin_curr_t or frhip_margin_bce_t (whose
+// forward folds its partials with bce.hip's row fold instead of the max / sum-exp merge, and whose recompute gets no row statistics).  sub = false: head_kernel (K is not read);
 // sub = true: head_sub_kernel over K planes, K = 1 included.  Every argument is validated before anything is launched.
 template <typename D>
 static int head_fwd_impl(const char* who, int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
@@ -636,6 +708,8 @@ static int head_fwd_impl(const char* who, int dtype, const void* ehat, const voi
     HeadArgs a = {};
     a.ehat = ehat; a.what = what; a.labels = labels; a.pmax = part_max; a.psum = part_sum; a.zt = ztarget; a.tsub = tsub;
     if ((rc = head_launch<true>(dtype, g, a, hm, sub ? K : 0, stream))) return rc;
+    if constexpr (std::is_same<D, frhip_margin_bce_t>::value)
+        return bce_rowfold_launch(part_max, part_sum, frhip_head_groups(classes), n, rowmax, rowsum, stream, who);
     hipLaunchKernelGGL(head_rowreduce_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, part_max, part_sum,
                        frhip_head_groups(classes), n, rowmax, rowsum);
     char tag[64];
@@ -903,6 +977,46 @@ extern "C" int frhip_head_bwd_dt_sub_curr(int dtype, const void* ehat, const voi
                                           hipStream_t stream) {
     return head_bwd_dt_impl("frhip_head_bwd_dt_sub_curr", dtype, ehat, what, labels, n, classes, d, true, subcenters, margin, rowmax,
                             rowsum, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
+}
+
+// ---- the sigmoid (BCE) head: the four with its descriptor; null operands are refused here, everything else by the shared checks
+static int bce_ptrs(const char* who, int dtype, bool ok) {
+    if (const int rc = by_dtype(dtype, who, [](auto) { return FRHIP_OK; })) return rc;       // an unknown dtype is refused first, everywhere
+    if (!ok) { set_error("%s: null pointer among the operands", who); return FRHIP_EINVAL; }
+    return FRHIP_OK;
+}
+
+extern "C" int frhip_head_fwd_bce(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                                  const frhip_margin_bce_t* margin, float* part_loss, float* part_db, float* ztarget, float* rowloss,
+                                  float* rowdb, hipStream_t stream) {
+    if (const int rc = bce_ptrs("frhip_head_fwd_bce", dtype, ehat && what && labels && part_loss && part_db && ztarget && rowloss && rowdb)) return rc;
+    return head_fwd_impl("frhip_head_fwd_bce", dtype, ehat, what, labels, n, classes, d, false, 1, margin, part_loss, part_db, ztarget,
+                         nullptr, rowloss, rowdb, stream);
+}
+
+extern "C" int frhip_head_fwd_sub_bce(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                                      int subcenters, const frhip_margin_bce_t* margin, float* part_loss, float* part_db, float* ztarget,
+                                      int* tsub, float* rowloss, float* rowdb, hipStream_t stream) {
+    if (const int rc = bce_ptrs("frhip_head_fwd_sub_bce", dtype,
+                                ehat && what && labels && part_loss && part_db && ztarget && tsub && rowloss && rowdb)) return rc;
+    return head_fwd_impl("frhip_head_fwd_sub_bce", dtype, ehat, what, labels, n, classes, d, true, subcenters, margin, part_loss, part_db,
+                         ztarget, tsub, rowloss, rowdb, stream);
+}
+
+extern "C" int frhip_head_bwd_dt_bce(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                                     const frhip_margin_bce_t* margin, float gscale, const float* upstream, void* dt, int ldt, void* dtt,
+                                     int ldtt, hipStream_t stream) {
+    if (const int rc = bce_ptrs("frhip_head_bwd_dt_bce", dtype, ehat && what && labels && dt)) return rc;
+    return head_bwd_dt_impl("frhip_head_bwd_dt_bce", dtype, ehat, what, labels, n, classes, d, false, 1, margin, nullptr, nullptr, gscale,
+                            upstream, dt, ldt, 0, dtt, ldtt, stream);
+}
+
+extern "C" int frhip_head_bwd_dt_sub_bce(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                                         int subcenters, const frhip_margin_bce_t* margin, float gscale, const float* upstream, void* dt,
+                                         int ldt, int ldp, void* dtt, int ldtt, hipStream_t stream) {
+    if (const int rc = bce_ptrs("frhip_head_bwd_dt_sub_bce", dtype, ehat && what && labels && dt)) return rc;
+    return head_bwd_dt_impl("frhip_head_bwd_dt_sub_bce", dtype, ehat, what, labels, n, classes, d, true, subcenters, margin, nullptr,
+                            nullptr, gscale, upstream, dt, ldt, ldp, dtt, ldtt, stream);
 }
 
 extern "C" int frhip_l2norm_rows(int dtype, const float* x, void* xhat, float* norms, int rows, int d, float eps,

@@ -1,6 +1,6 @@
 // What the fused head (head.hip) and the explicit-logit kernels (margin.hip) share so the two cannot drift apart: the margin constants,
-// the validity tests of the margin descriptors (frhip_margin_t, frhip_margin_rows_t, frhip_margin_curr_t in frhip.h), the target element
-// of the per-row margin and both elements of CurricularFace.
+// the validity tests of the margin descriptors (frhip_margin_t, frhip_margin_rows_t, frhip_margin_curr_t, frhip_margin_bce_t in
+// frhip.h), the target element of the per-row margin, both elements of CurricularFace and both elements of the sigmoid (BCE) head.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -67,5 +67,72 @@ __device__ __forceinline__ float curr_negative(float c, float thr, float tt, flo
     slope = 1.f;
     return c;
 }
+
+// ---- the sigmoid (binary cross-entropy) head: UniFace / SphereFace2 (frhip_margin_bce_t in frhip.h)
+// What the kernels take: ArcFace's constants of (s, m) for kind ARC (m3 = 0), or m3 = m for kind COS; the negatives' additive margin,
+// the two weights and the device scalar b.
+struct MarginBce : MarginConst { float m3, m_neg, w_pos, w_neg; int arc; const float* bias; };
+
+// nullptr for a descriptor the kernels implement, else what is wrong with it (for frhip_last_error)
+inline const char* margin_bce_desc_error(const frhip_margin_bce_t* mg) {
+    if (!mg) return "null descriptor";
+    if (!mg->bias) return "null bias";
+    if (mg->kind != FRHIP_MARGIN_ARCFACE && mg->kind != FRHIP_MARGIN_COSFACE) return "kind is neither ARCFACE nor COSFACE";
+    if (!(mg->s > 0.f) || !std::isfinite(mg->s)) return "s must be positive and finite";
+    if (!std::isfinite(mg->m) || !std::isfinite(mg->m_neg)) return "m and m_neg must be finite";
+    if (mg->kind == FRHIP_MARGIN_ARCFACE && !(mg->m >= 0.f && mg->m < 3.14159265358979f)) return "ARCFACE needs m in [0, pi)";
+    if (!(mg->w_pos >= 0.f) || !(mg->w_neg >= 0.f) || !std::isfinite(mg->w_pos) || !std::isfinite(mg->w_neg))
+        return "w_pos and w_neg must be finite and >= 0";
+    if (mg->w_pos == 0.f && mg->w_neg == 0.f) return "w_pos and w_neg are both 0";
+    return nullptr;
+}
+
+inline MarginBce margin_bce(const frhip_margin_bce_t* mg) {
+    MarginBce mb;
+    const bool arc = mg->kind == FRHIP_MARGIN_ARCFACE;
+    static_cast<MarginConst&>(mb) = margin_const(mg->s, arc ? mg->m : 0.f);
+    mb.m3 = arc ? 0.f : mg->m;
+    mb.m_neg = mg->m_neg; mb.w_pos = mg->w_pos; mb.w_neg = mg->w_neg;
+    mb.arc = arc ? 1 : 0;
+    mb.bias = mg->bias;
+    return mb;
+}
+
+// softplus(x) = log(1 + exp(x)) = max(x, 0) + log1p(exp(-|x|)): keeps its relative accuracy for x << 0, where log(1 + e) rounds to 0
+// (at 122 000 classes nearly every negative term is that small)
+__device__ __forceinline__ float bce_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+
+// sigmoid(a) from e = exp(-|a|): 1 / (1 + e) for a >= 0, e / (1 + e) below -- no overflow, full relative accuracy in both tails
+__device__ __forceinline__ float bce_sigmoid(float a) {
+    const float e = expf(-fabsf(a));
+    return (a >= 0.f ? 1.f : e) / (1.f + e);
+}
+
+// One element, on a cosine c already clamped to [-1, 1]; b = *mc.bias.  Both return the element's loss term and set a (the argument of
+// the sigmoid), dcos = d term / d c (the caller zeroes it where the clamp of the raw cosine binds) and db = d term / d b.
+// The target: a = s phi(c) - b, phi ArcFace's rule (curr_target, value and slope) or c - m; term w_pos softplus(-a).
+__device__ __forceinline__ float bce_target(float c, const MarginBce& mc, float b, float& a, float& dcos, float& db) {
+    float slope = 1.f, phi;
+    if (mc.arc) phi = curr_target(c, mc, slope);
+    else phi = c - mc.m3;
+    a = fmaf(mc.s, phi, -b);
+    const float sg = mc.w_pos * bce_sigmoid(-a);
+    dcos = -sg * mc.s * slope;
+    db = sg;
+    return mc.w_pos * bce_softplus(-a);
+}
+
+// A non-target: a = s (c + m_neg) - b; term w_neg softplus(a).
+__device__ __forceinline__ float bce_negative(float c, const MarginBce& mc, float b, float& a, float& dcos, float& db) {
+    a = fmaf(mc.s, c + mc.m_neg, -b);
+    const float sg = mc.w_neg * bce_sigmoid(a);
+    dcos = sg * mc.s;
+    db = -sg;
+    return mc.w_neg * bce_softplus(a);
+}
+
+// bce.hip: rowloss[m] = sum_g part_loss[g][m], rowdb likewise, in float64 and in group order; launched by the head's forward entry points
+int bce_rowfold_launch(const float* part_loss, const float* part_db, int groups, int n, float* rowloss, float* rowdb, hipStream_t stream,
+                       const char* who);
 
 }  // namespace frhip

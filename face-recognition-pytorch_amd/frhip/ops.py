@@ -825,6 +825,25 @@ def _margin_curr_desc(margin, n):
     return _MarginCurrDesc(float(margin.s), float(margin.m), _p(margin.thr), _p(margin.t))
 
 
+class _MarginBceDesc(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("s", ctypes.c_float), ("m", ctypes.c_float), ("m_neg", ctypes.c_float),
+                ("w_pos", ctypes.c_float), ("w_neg", ctypes.c_float), ("bias", ctypes.c_void_p)]
+
+
+def _is_bce(margin):
+    """the sigmoid head (frhip_margin_bce_t), e.g. nets.ArcFace.BceMargin: fields kind, s, m, m_neg, w_pos, w_neg and the device scalar bias"""
+    return hasattr(margin, "bias")
+
+
+def _margin_bce_desc(margin):
+    """The descriptor's values are judged by the library (one place, with its message); here only what ctypes cannot express"""
+    _need_cuda("BCE margin", bias=margin.bias)
+    if margin.bias.dtype != torch.float32 or margin.bias.numel() != 1:
+        raise ValueError("the BCE head's bias must be one float32 element, got %s %s" % (margin.bias.dtype, tuple(margin.bias.shape)))
+    return _MarginBceDesc(int(margin.kind), float(margin.s), float(margin.m), float(margin.m_neg), float(margin.w_pos),
+                          float(margin.w_neg), _p(margin.bias))
+
+
 def adaface_margins(norms, m, h, t_alpha, eps, batch_mean, batch_std, update):
     """AdaFace's per-row margins (m_ang, m_add) from the embedding norms [n] of the global batch in ONE launch (frhip_adaface_margins);
     update: the running batch_mean / batch_std (device scalars, fp32) are advanced in place first, else only read.  No host sync."""
@@ -987,13 +1006,17 @@ def _head_margin(margin, s, m, n, k):
         return "_rows", _margin_rows_desc(margin, n)
     if margin is not None and _is_curr(margin):
         return "_curr", _margin_curr_desc(margin, n)
+    if margin is not None and _is_bce(margin):
+        return "_bce", _margin_bce_desc(margin)
     return ("" if k > 1 else "_ex"), _margin_desc((MARGIN_ARCFACE, 0, s, m, 0.0) if margin is None else margin)
 
 
 def head_fwd(ehat, what, labels_i32, s, m, margin=None, subcenters=1):
     """margin=None: ArcFace(s, m) (frhip_head_fwd); a (kind, easy, s, m, filter_thr) descriptor (frhip_head_fwd_ex); or per-row
     margins (s, eps, m_ang, m_add), e.g. nets.ArcFace.RowMargins (frhip_head_fwd_rows); or CurricularFace's (s, m, thr, t), e.g.
-    nets.ArcFace.CurrRows (frhip_head_fwd_curr).
+    nets.ArcFace.CurrRows (frhip_head_fwd_curr); or the sigmoid head's (kind, s, m, m_neg, w_pos, w_neg, bias), e.g. nets.ArcFace.BceMargin
+    (frhip_head_fwd_bce): no softmax -- the result is then (ztarget, rowloss, rowdb[, tsub]), the rows' UNSCALED sums of the loss and
+    bias-gradient terms, for bce_reduce / bce_merge.
     subcenters = K > 1 (frhip_head_fwd_sub / _sub_rows): what holds K x classes rows, plane-major (row k * classes + c); a class's cosine is
     the maximum over its K centres and the result gains tsub [n] int32, the winning centre of each row's target (-1: no target on this shard)."""
     k = _check_subcenters(what, subcenters)
@@ -1088,7 +1111,7 @@ def head_dw_sub(dt, ehat, what, wnorm, out_scale=1.0):
 
 def head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, gscale, upstream=None, transposed=False, margin=None, subcenters=1):
     """dT [n][classes padded]; transposed=True: also dTt [classes][n padded] from the same launch -> (dT, dTt).
-    margin: as in head_fwd.
+    margin: as in head_fwd; the sigmoid head's (frhip_head_bwd_dt_bce) reads no row statistics: rmax, rsum are ignored (pass None).
     subcenters = K > 1 (what: K x classes rows, plane-major): dT is [n][K][classes padded] -- plane k holds d loss / d cos where centre k
     won its (row, class) and an exact 0 elsewhere, pad columns 0 -- and dTt is [K x classes][n padded], row k * classes + c."""
     k = _check_subcenters(what, subcenters)
@@ -1113,6 +1136,8 @@ def head_bwd_dt(ehat, what, labels_i32, s, m, rmax, rsum, gscale, upstream=None,
     mg = (s, m) if desc is None else (ctypes.byref(desc),)
     head = (dt_of(ehat), _p(ehat), _p(what), _p(labels_i32), n, classes, d)
     stats = (_p(rmax), _p(rsum), gscale, _p(upstream), _p(dt))
+    if suffix == "_bce":
+        stats = stats[2:]
     if k > 1:
         name = "frhip_head_bwd_dt_sub" + suffix
         check(getattr(lib(), name)(*head, k, *mg, *stats, k * ldp, ldp, _p(dtt), ldtt, _s()), name)
@@ -1191,6 +1216,50 @@ def margin_bwd_curr(gout, logits, labels_i64, margin):
     gin = torch.empty_like(gout)
     check(lib().frhip_margin_bwd_curr(_p(gout), _p(logits), _p(labels_i64), n, c, ctypes.byref(desc), _p(gin), _s()),
           "frhip_margin_bwd_curr")
+    return gin
+
+
+def bce_reduce(rowloss, rowdb):
+    """rowloss, rowdb [n] -> pair [2] fp32: this rank's UNSCALED sums, ONE one-workgroup launch in float64 (frhip_bce_reduce)"""
+    _need_f32("bce_reduce", rowloss=rowloss, rowdb=rowdb)
+    if rowloss.numel() != rowdb.numel() or not rowloss.is_contiguous() or not rowdb.is_contiguous():
+        raise ValueError("bce_reduce: rowloss and rowdb must be contiguous vectors of one length, got %s, %s"
+                         % (tuple(rowloss.shape), tuple(rowdb.shape)))
+    pair = torch.empty((2,), dtype=torch.float32, device=rowloss.device)
+    check(lib().frhip_bce_reduce(_p(rowloss), _p(rowdb), rowloss.numel(), _p(pair), _s()), "frhip_bce_reduce")
+    return pair
+
+
+def bce_merge(gathered, n_global):
+    """gathered [ws, 2] (the all-gathered bce_reduce pairs; [2]: one rank) -> (loss [1], dbias [1]), folded in rank order in float64 and
+    scaled by 1 / n_global (frhip_bce_merge)"""
+    _need_f32("bce_merge", gathered=gathered)
+    gathered = gathered.reshape(-1, 2)
+    if not gathered.is_contiguous():
+        raise ValueError("bce_merge: gathered must be contiguous")
+    out = torch.empty((2,), dtype=torch.float32, device=gathered.device)
+    check(lib().frhip_bce_merge(_p(gathered), gathered.shape[0], int(n_global), _p(out[0:1]), _p(out[1:2]), _s()), "frhip_bce_merge")
+    return out[0:1], out[1:2]
+
+
+def bce_fwd(logits, labels_i64, margin):
+    """explicit cosines [n, c] fp32 -> (rowloss [n], rowdb [n]): the sigmoid head's UNSCALED row sums (frhip_bce_fwd); margin: BceMargin"""
+    _need_f32("bce_fwd", logits=logits)
+    n, c = logits.shape
+    desc = _margin_bce_desc(margin)
+    out = torch.empty((2, n), dtype=torch.float32, device=logits.device)
+    check(lib().frhip_bce_fwd(_p(logits), _p(labels_i64), n, c, ctypes.byref(desc), _p(out[0]), _p(out[1]), _s()), "frhip_bce_fwd")
+    return out[0], out[1]
+
+
+def bce_bwd(logits, labels_i64, margin, gscale, upstream=None):
+    """-> gin [n, c] = d (sum of the terms) / d logits x gscale x *upstream (frhip_bce_bwd)"""
+    _need_f32("bce_bwd", logits=logits)
+    n, c = logits.shape
+    desc = _margin_bce_desc(margin)
+    gin = torch.empty_like(logits)
+    check(lib().frhip_bce_bwd(_p(logits), _p(labels_i64), n, c, ctypes.byref(desc), float(gscale), _p(upstream), _p(gin), _s()),
+          "frhip_bce_bwd")
     return gin
 
 

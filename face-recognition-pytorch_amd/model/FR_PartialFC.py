@@ -2,7 +2,8 @@
 
 Kept from /root/reference/model/FR_PartialFC.py: `Model(conf, logger, stage)` with `.encoder`, `.loss`, `.opt`,
 `.sch`, `.forward(x)` (:154-156), `.training_step(batch) -> {'loss': np.ndarray}` (:162-193),
-`.configure_optimizers()` (:434-474, ONE optimizer over param groups [encoder, head], head group last),
+`.configure_optimizers()` (:434-474, ONE optimizer over param groups [encoder, head], head group last; a margin with parameters of its
+own -- nets.ArcFace.UniFace's threshold -- gets a group between the two),
 `.training_epoch_end`, `.validation_step/.test_step(+_epoch_end)` (:196-373) and `.cross_test_step/_epoch_end` (:379-427).  The step composition is the reference's:
     opt.zero_grad -> encoder.train() -> feat = normalize(encoder(img)) -> loss = head(feat, id, opt)
     -> loss.backward() -> clip_grad_norm_(encoder, 5) -> opt.step()
@@ -296,6 +297,14 @@ class Model(nn.Module):
     def configure_optimizers(self):
         c = self.conf
         groups = [{"params": self.encoder.parameters()}, {"params": self.loss.parameters()}]
+        margin_params = list(getattr(self.loss, "margin_softmax", nn.Module()).parameters())
+        if margin_params:
+            # a margin with learnable parameters (UniFace's threshold): [encoder, margin (no weight decay), head].  The class centres stay
+            # LAST and alone: PartialFC swaps param_groups[-1]["params"][0] when it samples, and its early update fires only for a last
+            # group of exactly one parameter
+            ids = {id(p) for p in margin_params}
+            groups = [groups[0], {"params": margin_params, "weight_decay": 0.0},
+                      {"params": [p for p in self.loss.parameters() if id(p) not in ids]}]
         if c.optimizer == "AdamW":
             opt = importlib.import_module("frhip.optim").AdamW(groups, lr=self.lr, weight_decay=c.wd, eps=c.eps, betas=c.betas)
         elif c.optimizer == "SGD":

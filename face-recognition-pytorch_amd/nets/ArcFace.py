@@ -14,6 +14,9 @@ same with a margin that grows with the norm; its regulariser and the gradient th
 every step, and with `plus` hands the draws out by difficulty: `forward(logits, labels)`, a new tensor as well.
 `CurricularFace(s, m, alpha)` (Huang et al., CVPR 2020; not in the reference) re-weights the hard NEGATIVES of every row by a running mean
 of the target cosines: `forward(logits, labels)`, a new tensor as well.
+`UniFace(s, m, kind, w_pos, w_neg, m_neg, bias_init, learn_bias)` (Zhou et al., ICCV 2023; SphereFace2 with t = 1; not in the reference) is
+no softmax at all: every (row, class) pair is a sigmoid problem against one learnable threshold `bias`, and `forward(logits, labels)`
+returns the 0-dim LOSS, not logits.
 
 Inside PartialFC the margin is not applied through this `forward`: it lives in the epilogue of the fused cos-theta
 MFMA kernel (frhip_head_fwd / frhip_head_fwd_ex), which only reads the module's constants through `margin_of`, so the
@@ -47,14 +50,22 @@ ElasticMargin = collections.namedtuple("ElasticMargin", "s m std kind plus seed 
 CurricularMargin = collections.namedtuple("CurricularMargin", "s m alpha")
 CurrRows = collections.namedtuple("CurrRows", "s m thr t")
 
+# The sigmoid (BCE) head: the constants of the UniFace module (kind ARCFACE / COSFACE: the target's rule; m_neg: additive margin of the
+# negatives; w_pos, w_neg: the two weights), and what the kernels take: the same plus the device scalar bias (frhip_margin_bce_t)
+UniMargin = collections.namedtuple("UniMargin", "kind s m m_neg w_pos w_neg")
+BceMargin = collections.namedtuple("BceMargin", "kind s m m_neg w_pos w_neg bias")
+
 SUPPORTED = ("ArcFace, CosFace, CombinedMarginLoss (ArcFace m1 == 1, m3 == 0 or CosFace m3 > 0), AdaFace, MagFace, ElasticFace, "
-             "CurricularFace")
+             "CurricularFace, UniFace")
 
 
 def margin_of(module):
     """-> Margin of a margin module of this package, read from its attributes NOW (so a later `easy_margin = True` counts, as in
     the reference, whose modules read their attributes in forward); AdaMargin for AdaFace, MagMargin for MagFace, ElasticMargin for
-    ElasticFace, CurricularMargin for CurricularFace.  NotImplementedError for any other module."""
+    ElasticFace, CurricularMargin for CurricularFace, UniMargin for UniFace.  NotImplementedError for any other module."""
+    if isinstance(module, UniFace):
+        return UniMargin(UNIFACE_KINDS[module.kind], float(module.s), float(module.m), float(module.m_neg), float(module.w_pos),
+                         float(module.w_neg))
     if isinstance(module, CurricularFace):
         return CurricularMargin(float(module.s), float(module.m), float(module.alpha))
     if isinstance(module, ElasticFace):
@@ -403,3 +414,83 @@ class CurricularFace(torch.nn.Module):
 def _hip_curricular_rows(tcos, mg, t, update):
     from frhip import ops
     return ops.curricular_rows(tcos.float().contiguous(), mg.m, mg.alpha, t, update)
+
+
+UNIFACE_KINDS = {"arc": ARCFACE, "cos": COSFACE}
+
+
+class _UniFaceFn(torch.autograd.Function):
+    """the sigmoid head on explicit cosines (frhip_bce_fwd -> _reduce -> _merge; frhip_bce_bwd): -> the 0-dim loss, with gradients to the
+    logits and to the bias"""
+
+    @staticmethod
+    def forward(ctx, logits, bias, labels, mg):
+        from frhip import ops
+        if not logits.is_cuda:
+            raise RuntimeError("nets.ArcFace (frhip): logits must live on the MI355X; there is no CPU path")
+        lab = labels.reshape(-1).long().contiguous()
+        cos = logits.detach().float().contiguous()
+        b = bias.detach().clone()                         # by value: the optimizer moves the parameter on
+        bm = BceMargin(*mg, b)
+        n = cos.shape[0]
+        loss, dbias = ops.bce_merge(ops.bce_reduce(*ops.bce_fwd(cos, lab, bm)), n)
+        ctx.save_for_backward(cos, lab, b, dbias)
+        ctx.mg, ctx.shapes = mg, (logits.dtype, bias.shape)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        from frhip import ops
+        cos, lab, b, dbias = ctx.saved_tensors
+        up = g.reshape(1).float().contiguous()
+        gin = ops.bce_bwd(cos, lab, BceMargin(*ctx.mg, b), 1.0 / cos.shape[0], up)
+        return gin.to(ctx.shapes[0]), (up * dbias).reshape(ctx.shapes[1]), None, None
+
+
+class UniFace(torch.nn.Module):
+    """Unified cross-entropy (UniFace, Zhou et al., ICCV 2023): every class is a binary sigmoid problem against ONE threshold b.  With
+    c the cosine clamped to [-1, 1]: the target contributes w_pos softplus(-(s phi(c) - b)), phi(c) = c - m (kind "cos") or ArcFace's
+    cos(theta + m) / c - m sin(pi - m) (kind "arc"); every other class w_neg softplus(s (c + m_neg) - b); the loss is their sum over
+    all rows and all classes (of all shards; with sampling the activated ones) divided by the global batch size.  An element's gradient
+    depends on nothing outside the element, so a class-sharded backward pass needs nothing from the other shards.
+    `bias` is a [1] fp32 Parameter (a buffer with learn_bias=False); bias_init=None means log(10 x num_classes), set by
+    reset_bias(num_classes) -- PartialFC calls it at construction, the stand-alone user once the class count is known.
+    SphereFace2 (Wen et al., ICLR 2022) with its similarity adjustment g(z) = 2 ((z + 1) / 2)^t - 1 at t = 1 is this module with
+    s = r, m_neg = m, w_pos = lambda / r, w_neg = (1 - lambda) / r; t != 1 is not built."""
+    def __init__(self, s=64.0, m=0.4, kind="cos", w_pos=1.0, w_neg=1.0, m_neg=0.0, bias_init=None, learn_bias=True):
+        super().__init__()
+        if kind not in UNIFACE_KINDS:
+            raise ValueError("UniFace: kind must be 'arc' or 'cos', got %r" % (kind,))
+        if not (s > 0 and math.isfinite(s)):
+            raise ValueError("UniFace: s must be positive and finite, got %r" % (s,))
+        if not (math.isfinite(m) and math.isfinite(m_neg)):
+            raise ValueError("UniFace: m and m_neg must be finite, got %r, %r" % (m, m_neg))
+        if kind == "arc" and not 0.0 <= m < math.pi:
+            raise ValueError("UniFace: kind 'arc' needs m in [0, pi), got %r" % (m,))
+        if not (w_pos >= 0 and w_neg >= 0 and math.isfinite(w_pos) and math.isfinite(w_neg)) or (w_pos == 0 and w_neg == 0):
+            raise ValueError("UniFace: w_pos and w_neg must be finite, >= 0 and not both 0, got %r, %r" % (w_pos, w_neg))
+        if bias_init is not None and not math.isfinite(bias_init):
+            raise ValueError("UniFace: bias_init must be finite, got %r" % (bias_init,))
+        self.s, self.m, self.kind = s, m, kind
+        self.w_pos, self.w_neg, self.m_neg = w_pos, w_neg, m_neg
+        self.scale, self.margin = s, m
+        self.bias_init, self.learn_bias = bias_init, bool(learn_bias)
+        b = torch.full((1,), float(bias_init) if bias_init is not None else 0.0, dtype=torch.float32)
+        if self.learn_bias:
+            self.bias = torch.nn.Parameter(b)
+        else:
+            self.register_buffer("bias", b)
+
+    @torch.no_grad()
+    def reset_bias(self, num_classes):
+        """bias <- bias_init, or log(10 x num_classes) (the GLOBAL class count) when bias_init is None"""
+        if num_classes < 1:
+            raise ValueError("UniFace.reset_bias: num_classes must be >= 1, got %r" % (num_classes,))
+        self.bias.fill_(float(self.bias_init) if self.bias_init is not None else math.log(10.0 * num_classes))
+
+    def forward(self, logits: torch.Tensor, labels: torch.Tensor):
+        """explicit cosines [N, C] (labels [N] or [N, 1], -1 = no target) -> the 0-dim loss (mean over the N rows of the rows' sums),
+        differentiable in `logits` and in `bias`.  It is NOT a logit tensor: nothing downstream is a softmax."""
+        if self.bias.device != logits.device:
+            raise RuntimeError("nets.ArcFace (frhip): UniFace's bias must live on the logits' device: module.to(device)")
+        return _UniFaceFn.apply(logits, self.bias, labels, margin_of(self))

@@ -26,7 +26,8 @@ What runs where
     (seed, step, row) with no collective at all (frhip_elastic_margins); its "+" variants add one all-gather of the rows' target cosines
     ([N] floats per rank, frhip_head_target_cos), which every rank merges and ranks itself (frhip_elastic_assign).  CurricularFace
     gathers the same target cosines and turns them into per-row thresholds and its running mean t on every rank (frhip_curricular_rows,
-    one launch).
+    one launch).  UniFace (the sigmoid head, `_BceHeadFn`) is no softmax: instead of the [N][3] triples the ranks all-gather TWO scalars,
+    their sums of the loss and of the threshold's gradient, and the backward pass waits for no row statistics.
 `conf.subcenters = K` (not in the reference; sub-center ArcFace): every class owns K centres, the table is plane-major [K x num_local, D]
 (centre k of class c in row k * num_local + c), the fused kernels take the maximum over a class's centres on their accumulators and send
 its gradient to the winner alone; sampling, sharding and the collectives stay at class level.  Absent or 1: the calls made before.
@@ -40,8 +41,9 @@ from typing import Callable
 import torch
 from torch import distributed
 
-from .ArcFace import (SUPPORTED as SUPPORTED_MARGINS, AdaFace, AdaMargin, ArcFace, CombinedMarginLoss, CosFace, CurricularFace,
-                      CurricularMargin, CurrRows, ElasticFace, ElasticMargin, MagFace, MagMargin, RowMargins, is_plain_arcface, margin_of)
+from .ArcFace import (SUPPORTED as SUPPORTED_MARGINS, AdaFace, AdaMargin, ArcFace, BceMargin, CombinedMarginLoss, CosFace, CurricularFace,
+                      CurricularMargin, CurrRows, ElasticFace, ElasticMargin, MagFace, MagMargin, RowMargins, UniFace, UniMargin,
+                      is_plain_arcface, margin_of)
 
 
 import os
@@ -99,6 +101,15 @@ class HipHeadKernels:
         """tcos [ws, n] of all ranks -> thr [n]: CurricularFace's per-row thresholds; update: t is advanced in the same launch.
         mg: nets.ArcFace.CurricularMargin"""
         return self.ops.curricular_rows(tcos, mg.m, mg.alpha, t, update)
+
+    def bce_reduce(self, rowloss, rowdb):
+        """the sigmoid head: forward_stats(margin=BceMargin) returned (ztarget, rowloss, rowdb[, tsub]), the rows' unscaled sums of the loss
+        and bias-gradient terms -> pair [2], this rank's sums (one one-workgroup launch, float64)"""
+        return self.ops.bce_reduce(rowloss, rowdb)
+
+    def bce_merge(self, gathered, n_global):
+        """gathered [ws, 2]: the pairs of all ranks -> (loss [1], dbias [1]), folded in rank order and scaled by 1 / n_global"""
+        return self.ops.bce_merge(gathered, n_global)
 
     def rescale(self, rowsum, local_max, global_max):
         self.ops.head_rescale(rowsum, local_max, global_max)
@@ -334,6 +345,65 @@ class _MarginSoftmaxFn(torch.autograd.Function):
         return d_n[rank * ctx.rows:(rank + 1) * ctx.rows].to(dtype).reshape(shape)
 
 
+class _BceHeadFn(torch.autograd.Function):
+    """all-gather -> normalise -> cos -> sigmoid (BCE) loss against the threshold `bias` (UniFace), as ONE autograd node over the fused
+    kernels, from the rank's LOCAL embeddings to the global loss.  Beside _MarginSoftmaxFn, not a switch in it: there is no softmax, so
+    no per-row statistics are exchanged -- each rank reduces its shard to the pair {sum of loss terms, sum of d/db terms}, the pairs are
+    all-gathered (two floats per rank) and folded in rank order, and the backward pass recomputes d loss / d cos from the element alone."""
+
+    @staticmethod
+    def forward(ctx, local_embeddings, weight_activated, bias, labels_i32, kern, mg, world_size, collectives, subcenters=1, sub_out=None):
+        """mg: nets.ArcFace.UniMargin; bias: the module's [1] fp32 threshold (a Parameter, or a buffer that needs no gradient).
+        subcenters, sub_out: as in _MarginSoftmaxFn"""
+        local_embeddings = local_embeddings.contiguous()
+        rows, dim = local_embeddings.shape
+        if collectives:
+            embeddings = _all_gather_flat(local_embeddings.new_empty((world_size * rows, dim)), local_embeddings)
+        else:
+            embeddings = local_embeddings
+        ehat, enorm = kern.normalize(embeddings)
+        what, wnorm = kern.normalize(weight_activated)
+        b = bias.detach().clone()                            # by value: the optimizer moves the parameter on before a later backward
+        margin = BceMargin(*mg, b)
+        sub = {"subcenters": subcenters} if subcenters > 1 else {}
+        zt, rowloss, rowdb, *tsub = kern.forward_stats(ehat, what, labels_i32, mg.s, mg.m, margin=margin, **sub)
+        if tsub and sub_out is not None:
+            sub_out.append(tsub[0])
+        pair = kern.bce_reduce(rowloss, rowdb)
+        if collectives:                                      # the ONE statistics exchange of this head: two scalars per rank
+            pair = _all_gather_flat(pair.new_empty(world_size * 2), pair)
+        loss, dbias = kern.bce_merge(pair.view(-1, 2), ehat.shape[0])
+        ctx.kern, ctx.mg, ctx.world_size, ctx.collectives, ctx.rows, ctx.sub = kern, mg, world_size, collectives, rows, sub
+        ctx.bias_like = (bias.shape, bias.dtype)
+        ctx.save_for_backward(ehat, enorm, what, wnorm, labels_i32, b, dbias)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        ehat, enorm, what, wnorm, labels_i32, b, dbias = ctx.saved_tensors
+        mg = ctx.mg
+        extra = dict({"margin": BceMargin(*mg, b)}, **ctx.sub)
+        up = grad_loss.reshape(1).float().contiguous()
+        d_bias = None
+        if ctx.needs_input_grad[2]:
+            d_bias = (up.to(dbias.dtype) * dbias).reshape(ctx.bias_like[0]).to(ctx.bias_like[1])
+        if not ctx.collectives:
+            d_e, d_w = ctx.kern.backward(ehat, enorm, what, wnorm, labels_i32, mg.s, mg.m, None, None, ehat.shape[0], up, **extra)
+            return (d_e, d_w, d_bias) + (None,) * 7
+        pending = []
+        rank = distributed.get_rank()
+
+        def start(d_e):
+            pending.append(_reduce_scatter_sum(d_e, rank, ctx.rows, async_op=True))
+
+        _, d_w = ctx.kern.backward(ehat, enorm, what, wnorm, labels_i32, mg.s, mg.m, None, None, ehat.shape[0], up,
+                                   e_scale=float(ctx.world_size), on_de=start, **extra)
+        d_local, work = pending[0]
+        if work is not None:
+            work.wait()
+        return (d_local, d_w, d_bias) + (None,) * 7
+
+
 class DistCrossEntropyFunc(torch.autograd.Function):
     """Explicit-logit softmax-CE across class shards (reference :435-484): in place on `logits`, three all-reduces.
     Row kernels of libfrhip (frhip_rows_max / _rows_exp_sum / _rows_normalize / _ce_grad); the backward scale is
@@ -417,9 +487,12 @@ class _PartialFCBase(torch.nn.Module):
             self.margin_softmax = margin_loss(conf.loss_s, conf.loss_m)
         else:
             raise
-        if not isinstance(self.margin_softmax, (ArcFace, CosFace, CombinedMarginLoss, AdaFace, MagFace, ElasticFace, CurricularFace)):
+        if not isinstance(self.margin_softmax, (ArcFace, CosFace, CombinedMarginLoss, AdaFace, MagFace, ElasticFace, CurricularFace,
+                                                UniFace)):
             raise NotImplementedError("the fused head kernel implements the margin modules %s, not %s"
                                       % (SUPPORTED_MARGINS, type(self.margin_softmax).__name__))
+        if isinstance(self.margin_softmax, UniFace):              # margin_loss(s, m) never saw the class count: the default threshold
+            self.margin_softmax.reset_bias(num_classes)           # log(10 x classes) is set here, once
         self._kernels = kernels
         self._conf = conf
         self.step = 0
@@ -694,6 +767,15 @@ class _PartialFCBase(torch.nn.Module):
         return self._margin_softmax(local_embeddings, labels.view(-1).to(torch.int32).contiguous(), s, m, collectives, tail)
 
     def _margin_softmax(self, local_embeddings, labels_i32, s, m, collectives, tail):
+        if isinstance(self.margin_softmax, UniFace):             # the sigmoid head: its own node, the threshold a tensor input
+            won = []
+            loss = _BceHeadFn.apply(local_embeddings, self.weight_activated, self.margin_softmax.bias, labels_i32, self.kernels,
+                                    margin_of(self.margin_softmax), self.world_size, collectives, self.subcenters, won)
+            if self.subcenters > 1:
+                self.last_target_sub = won[0]
+                if self.sub_hits is not None and self.training:
+                    self._count_sub_hits(labels_i32, won[0])
+            return loss
         if self.subcenters == 1:
             return _MarginSoftmaxFn.apply(local_embeddings, self.weight_activated, labels_i32, self.kernels, s, m,
                                           self.world_size, collectives, *tail)
@@ -792,6 +874,13 @@ class _PartialFCBase(torch.nn.Module):
             buf, src = self.margin_softmax.t, state_dict.get("margin_softmax.t")
             with torch.no_grad():
                 buf.copy_(src.to(buf.device).reshape(buf.shape)) if src is not None else buf.zero_()
+        if isinstance(self.margin_softmax, UniFace):              # the threshold is trained state: a checkpoint without it is refused
+            buf, src = self.margin_softmax.bias, state_dict.get("margin_softmax.bias")
+            if src is None:
+                raise KeyError("load_state_dict: this head's margin is UniFace, whose trained threshold travels as 'margin_softmax.bias'; "
+                               "the checkpoint has no such key (keys: %s)" % sorted(state_dict))
+            with torch.no_grad():
+                buf.copy_(src.to(buf.device).reshape(buf.shape))
         rows = self.subcenters * self.num_local
         if state_dict["weight"].dim() != 2 or state_dict["weight"].shape[0] != rows:
             raise ValueError("load_state_dict: this head holds %d sub-centre(s) x %d classes = %d rows (plane-major: row k * %d + c), "

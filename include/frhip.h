@@ -506,6 +506,48 @@ int frhip_head_bwd_dt_sub_curr(int dtype, const void* ehat, const void* what, co
                                float gscale, const float* upstream, void* dt, int ldt, int ldp, void* dtt, int ldtt,
                                frhip_stream_t stream);
 
+/* The sigmoid (binary cross-entropy) head (not in the reference: UniFace, Zhou et al., ICCV 2023; SphereFace2, Wen et al., ICLR 2022).
+ * Every (row, class) pair is a binary problem with ONE threshold b, so no element needs its row's statistics: the recompute kernel reads
+ * no row max / sum, and the ranks exchange two scalars per step instead of [n][3] triples.  With c = clamp(raw, -1, 1), gradient 0 where
+ * the clamp binds (loss and bias terms still count), with K sub-centres the pooled cosine, y_i the shard-relative label (-1: no target
+ * column on this shard), b = *bias read on the device by every launch (no host synchronisation, capturable):
+ *   target:     a = s phi(c) - b; kind COSFACE: phi = c - m, slope 1; kind ARCFACE: ArcFace's rule, cos(theta + m) above cos(pi - m),
+ *               c - m sin(pi - m) below, with its slope; term w_pos softplus(-a), d/dc = -w_pos sigmoid(-a) s slope, d/db = +w_pos sigmoid(-a);
+ *   non-target: a = s (c + m_neg) - b; term w_neg softplus(a), d/dc = w_neg sigmoid(a) s, d/db = -w_neg sigmoid(a);
+ *   loss = (1 / N_global) sum of the terms over all rows and all (activated) classes of all shards, dbias the same sum of the d/db;
+ *   classes >= `classes` of the last tile and rows >= n contribute exactly 0 to loss, dbias and dT (a padded column's cosine is 0: unmasked
+ *   it would add softplus(-b));
+ *   softplus(x) = max(x, 0) + log1p(exp(-|x|)); sigmoid(a) = (a >= 0 ? 1 : e) / (1 + e), e = exp(-|a|): relative accuracy in both tails.
+ * A descriptor is refused (FRHIP_EINVAL with a frhip_last_error text, nothing is launched) when it or its bias is null, kind is neither
+ * FRHIP_MARGIN_ARCFACE nor _COSFACE, s is not positive and finite, m or m_neg is not finite, ARCFACE has m outside [0, pi), a weight is
+ * negative or not finite, or both weights are 0. */
+typedef struct { int kind; float s, m, m_neg, w_pos, w_neg; const float* bias; } frhip_margin_bce_t;
+/* Forward: part_loss / part_db [frhip_head_groups(classes)][n]: the loss and bias-gradient partial sums of each 64-class column group
+ * (fp32, unscaled); ztarget[i] = a of row i's target (untouched where y_i = -1); tsub as in frhip_head_fwd_sub.  A second launch folds
+ * the partials into rowloss[n], rowdb[n] in float64, in group order (an order that depends on the shape alone).  Bad shape / dtype,
+ * subcenters outside 1 .. frhip_head_sub_max(), a null pointer or a bad descriptor: FRHIP_EINVAL, nothing is launched. */
+int frhip_head_fwd_bce(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                       const frhip_margin_bce_t* margin, float* part_loss, float* part_db, float* ztarget, float* rowloss, float* rowdb,
+                       frhip_stream_t stream);
+int frhip_head_fwd_sub_bce(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d, int subcenters,
+                           const frhip_margin_bce_t* margin, float* part_loss, float* part_db, float* ztarget, int* tsub, float* rowloss,
+                           float* rowdb, frhip_stream_t stream);
+/* Recompute: dT / dTt as frhip_head_bwd_dt / _sub write them, = d loss / d cos x gscale (x *upstream when not NULL).  Takes no row
+ * statistics.  Bad pitches are refused as there. */
+int frhip_head_bwd_dt_bce(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d,
+                          const frhip_margin_bce_t* margin, float gscale, const float* upstream, void* dt, int ldt, void* dtt, int ldtt,
+                          frhip_stream_t stream);
+int frhip_head_bwd_dt_sub_bce(int dtype, const void* ehat, const void* what, const int* labels, int n, int classes, int d, int subcenters,
+                              const frhip_margin_bce_t* margin, float gscale, const float* upstream, void* dt, int ldt, int ldp, void* dtt,
+                              int ldtt, frhip_stream_t stream);
+/* rowloss[n], rowdb[n] -> pair[2] = {sum of rowloss, sum of rowdb}: this rank's UNSCALED sums.  ONE workgroup, float64 accumulation in
+ * an order fixed by n, rounded once to fp32.  n < 1 or a null pointer: FRHIP_EINVAL. */
+int frhip_bce_reduce(const float* rowloss, const float* rowdb, int n, float* pair, frhip_stream_t stream);
+/* gathered [world_size][2]: the pairs of all ranks (world_size 1: this rank's own) -> loss[0] = (sum_r pair_r[0]) / n_global,
+ * dbias[0] = (sum_r pair_r[1]) / n_global, folded in rank order in float64 (every rank gets the same bits).  The 1 / N_global scaling
+ * is applied HERE, once.  world_size < 1, n_global < 1 or a null pointer: FRHIP_EINVAL. */
+int frhip_bce_merge(const float* gathered, int world_size, int n_global, float* loss, float* dbias, frhip_stream_t stream);
+
 /* ---- bn1 -> relu -> conv2 of a BasicBlock (nets/resnet.py:91-93) WITHOUT the activated tensor: the BatchNorm-apply + ReLU
  * is folded into the operand path of the convolution (forward) and of its weight gradient, which read the saved BatchNorm
  * INPUT x and form relu(x * in_scale[c] + in_shift[c]) in LDS.  bf16, 3x3 / stride 1 / pad 1; *_fusable() tells whether a
@@ -606,6 +648,14 @@ int frhip_margin_fwd_curr(const float* logits, const int64_t* labels, int n, int
                           frhip_stream_t stream);
 int frhip_margin_bwd_curr(const float* gout, const float* logits, const int64_t* labels, int n, int c,
                           const frhip_margin_curr_t* margin, float* gin, frhip_stream_t stream);
+/* The sigmoid head's rule (frhip_margin_bce_t above; UniFace.forward stand-alone) on explicit cosines [n][c], int64 labels (-1: no
+ * target).  fwd: rowloss[i] / rowdb[i] = the UNSCALED sums of row i's loss and bias-gradient terms (float64 accumulation; feed
+ * frhip_bce_reduce / frhip_bce_merge).  bwd: gin[i][j] = d term / d logits x gscale (x *upstream when not NULL), 0 where the clamp binds.
+ * Logits stay untouched.  n < 1, c < 1, a null pointer or a bad descriptor: FRHIP_EINVAL, nothing is launched. */
+int frhip_bce_fwd(const float* logits, const int64_t* labels, int n, int c, const frhip_margin_bce_t* margin, float* rowloss,
+                  float* rowdb, frhip_stream_t stream);
+int frhip_bce_bwd(const float* logits, const int64_t* labels, int n, int c, const frhip_margin_bce_t* margin, float gscale,
+                  const float* upstream, float* gin, frhip_stream_t stream);
 int frhip_rows_max(const float* x, int n, int c, float* rowmax, frhip_stream_t stream);
 int frhip_rows_exp_sum(float* x, int n, int c, const float* rowmax, float* rowsum, frhip_stream_t stream);
 int frhip_rows_normalize(float* x, int n, int c, const float* rowsum, const int64_t* labels, float* ptarget,
